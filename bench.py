@@ -14,7 +14,15 @@ size is fixed (strong scaling).  Under torch.distributed.run the ranks come from
 environment; `python bench.py --gpus N` alone starts the N ranks itself.  An RCCL failure is
 fatal; the host-staged gloo exchange is only used with --exchange-impl host.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config M|C2|C3|C4|C5|R]
+A plain run sets up, warms up, times the K steps and prints the result line (the headline
+rate and ms_per_step, the loop's statistics).  --full adds everything else the benchmark measures
+and checks, each outside the timed region: the trajectory check against the committed oracle
+data, the in-loop phase times, the evaluation roofline, the round-robin and streaming lines, the
+CPU baseline and, for N>1 with the replicated plan, the sharded line.  --dump-outputs DIR
+writes what the timed loop left after its last step as DIR/<name>.npy (dump_outputs).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config M|C2|C3|C4|C5|R] [--full]
+                       [--dump-outputs DIR]
 """
 import argparse
 import faulthandler
@@ -42,6 +50,8 @@ CONFIGS = {
 }
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 TRAJECTORY_JSON = os.path.join(ROOT, "tests", "golden", "bench_trajectory.json")
+DUMP_MAX_ELEMS = 4_000_000  # per dumped array: three float32 arrays of at most 16 MB each
+DUMP_SAMPLE_SEED = 20240607
 
 
 def log(*a):
@@ -133,7 +143,7 @@ def cpu_baseline(cfg, budget_s, full_iteration_cap_s=0.0):
             full = {"measured": False,
                     "why": ("one reference iteration at the full size takes ~1e3 s (its populate_mis_parallel is "
                             "quadratic in |U|: 158 s at m=4M on 8 threads, BASELINE.md), beyond the default "
-                            "line's few-minute budget; bench.py --cpu-full-iteration SECONDS runs it wall-capped")}
+                            "line's few-minute budget; bench.py --full --cpu-full-iteration SECONDS runs it wall-capped")}
         points[f"m={m}"] = full
         return {
             "value": loop_rate,
@@ -199,6 +209,44 @@ def trajectory_check(cfg, T, st, words, seed):
     out["got"] = dict(zip(("n_violated", "sum_mis_size", "n_resamples", "digest"), got[1:]))
     out["match"] = got == list(row)
     return out
+
+
+def _flags01(words, count, idx):
+    """0/1 float32 of the flags idx (all `count` of them when idx is None) out of a bit-packed
+    array (flag i = bit i & 31 of the 32-bit word i >> 5, little-endian host)."""
+    w = np.ascontiguousarray(words).view(np.uint32)
+    if idx is None:
+        idx = np.arange(count, dtype=np.int64)
+    return ((w[idx >> 5] >> (idx & 31).astype(np.uint32)) & np.uint32(1)).astype(np.float32)
+
+
+def read_outputs(s, n, m):
+    """What a caller of the timed loop receives after its last step: the statistics, the
+    assignment, the violated set and the MIS of the last iteration.  Arrays longer than
+    DUMP_MAX_ELEMS are a fixed sample (sorted indices drawn once from DUMP_SAMPLE_SEED, the same
+    for every run of the same configuration), so a dump stays below 64 MB at every config."""
+    def sample(count, stream):
+        if count <= DUMP_MAX_ELEMS:
+            return None
+        return np.sort(np.random.default_rng([DUMP_SAMPLE_SEED, stream]).integers(0, count, DUMP_MAX_ELEMS))
+
+    st = s.stats()
+    iv, ic = sample(n, 0), sample(m, 1)
+    in_mis = np.zeros(m, np.uint8)
+    in_mis[s.mis()] = 1
+    return {
+        "stats": np.array([st[q] for q in ("n_iterations", "n_resamples", "sum_mis_size", "avg_mis_size",
+                                           "n_violated", "solved")], np.float64),
+        "assignment": _flags01(s.assignment_words(), n, iv),
+        "violated": _flags01(s.violated_mask(), m, ic),
+        "mis": (in_mis if ic is None else in_mis[ic]).astype(np.float32),
+    }
+
+
+def dump_outputs(outputs, where):
+    os.makedirs(where, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(where, name + ".npy"), a)
 
 
 def rr_line(args, n, m, k, kind, Solver, generate_ksat, device, warmup=20, steps=10):
@@ -352,6 +400,12 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="M", choices=list(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run what lies outside the headline: trajectory check, phase times, roofline, "
+                         "round-robin and streaming lines, CPU baseline, N>1 sharded line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed loop left after its last step (statistics, assignment, violated "
+                         "set, MIS) as DIR/<name>.npy")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--exchange", default="allgather", choices=["allgather", "allreduce"])
     ap.add_argument("--exchange-impl", default="rccl", choices=["rccl", "host"],
@@ -414,13 +468,16 @@ def main():
 
     # The library (and with it the ROCm runtime it was built against) is loaded before torch:
     # torch's wheel bundles its own HIP runtime, which the library would otherwise bind to.
-    # torch is used for the rendezvous and the host-side collectives only (gloo); device
-    # synchronisation goes through the library (the solver's stream holds all of its work).
+    # torch is used for the rendezvous and the host-side collectives only (gloo), so one rank
+    # alone does without it; device synchronisation goes through the library (the solver's
+    # stream holds all of its work).
     from alllsatisfiabilitysolver_amd import Solver, comm_unique_id, generate_ksat
     from alllsatisfiabilitysolver_amd import _native as N
 
     N.lib()
-    import torch
+    torch = None
+    if world > 1:
+        import torch
 
     dist = None
     comm_id = None
@@ -476,7 +533,8 @@ def main():
         s = Solver(n, offs, lits, exchange=gloo_exchange(), **kw)
     else:
         s = Solver(n, offs, lits, comm_id=comm_id, **kw)  # RCCL failure raises: fatal
-    if not (plan == "replicate" and not args.no_shard_line):
+    shard_too = args.full and world > 1 and plan == "replicate" and not args.no_shard_line
+    if not shard_too:
         del offs, lits
     t_create = time.perf_counter() - t0
     log(f"[rank {rank}] generated {m} clauses in {t_gen:.2f}s, uploaded in {t_create:.2f}s, "
@@ -513,7 +571,9 @@ def main():
         dt = float(tt.item())
     st = s.stats()
     log(f"[rank {rank}] timed {st['n_iterations'] - it0} iterations in {dt:.3f}s")
-    traj = trajectory_check(args.config, 1, st, s.assignment_words(), args.seed) if rank == 0 else None
+    traj = trajectory_check(args.config, 1, st, s.assignment_words(), args.seed) if rank == 0 and args.full else None
+    if rank == 0 and args.dump_outputs:  # (before the eval-only launches and eager replays of --full)
+        dump_outputs(read_outputs(s, n, m), args.dump_outputs)
     # the timed loop must have replayed the captured graphs; an eager fallback (a capture or an
     # RCCL call under capture that failed) would time a different launch pattern unannounced
     graphs, graph_note = s.uses_graphs()
@@ -531,7 +591,7 @@ def main():
     # in-loop phase times of exactly the timed iterations, from the kernels' own device
     # wall-clock stamps (the graph replays as timed; eval = first workgroup start to last
     # workgroup end); the eval kernel's average duration prices the roofline
-    pt = s.loop_times(it0, max(1, steps_done))
+    pt = s.loop_times(it0, max(1, steps_done)) if args.full else None
     eval_bytes = s.eval_bytes()
     # The roofline's kernel is the evaluation alone (k_eval_hybrid<K>): HIP events on the
     # solver's stream around back-to-back eval-only launches after the timed region (on the
@@ -539,27 +599,31 @@ def main():
     # fused with the round-0 scatter (k_eval_scatter<K>), whose duration is not the
     # evaluation's; its evaluation part (the kernels' wall-clock stamps) is reported beside it.
     # (a converging instance's clause-eval rate is the same eval-only rate.)
-    ev_ms = s.bench_eval(max(args.eval_b2b, 20))[0]
-    eval_ms = ev_ms
-    achieved = eval_bytes / (eval_ms * 1e-3) / 1e9 if eval_ms > 0 else 0.0
-    achieved_loop = eval_bytes / (pt["eval_ms"] * 1e-3) / 1e9 if pt["eval_ms"] > 0 else 0.0
-    # cross-check with HIP events on the solver's stream: the same iteration replayed eagerly
-    pe = s.profile(args.event_iters) if args.event_iters > 0 and not converged else None
-    traffic = None
-    try:
-        tj = json.load(open(args.traffic_json))
-        if tj.get("config") == args.config and tj.get("n_gpus", 1) == world:
-            traffic = tj.get("hbm_bytes_per_launch")
-            # (the roofline prices the evaluation alone: its own kernel's counters when recorded)
-            for k, v in (tj.get("per_kernel") or {}).items():
-                if s.eval_kernel() in k.split("(")[0] and "hbm_bytes_per_launch" in v:
-                    traffic = v["hbm_bytes_per_launch"]
-    except (OSError, ValueError):
-        pass
+    # (a plain run makes these launches only where its headline needs them: the loop converged
+    # or stopped short, and the evaluation pass rate stands in for the loop rate)
+    loop_rate = steps_done == args.steps and not converged
+    eval_ms = s.bench_eval(max(args.eval_b2b, 20))[0] if args.full or not loop_rate else None
+    achieved = achieved_loop = 0.0
+    pe = traffic = None
+    if args.full:
+        achieved = eval_bytes / (eval_ms * 1e-3) / 1e9 if eval_ms > 0 else 0.0
+        achieved_loop = eval_bytes / (pt["eval_ms"] * 1e-3) / 1e9 if pt["eval_ms"] > 0 else 0.0
+        # cross-check with HIP events on the solver's stream: the same iteration replayed eagerly
+        pe = s.profile(args.event_iters) if args.event_iters > 0 and not converged else None
+        try:
+            tj = json.load(open(args.traffic_json))
+            if tj.get("config") == args.config and tj.get("n_gpus", 1) == world:
+                traffic = tj.get("hbm_bytes_per_launch")
+                # (the roofline prices the evaluation alone: its own kernel's counters when recorded)
+                for k, v in (tj.get("per_kernel") or {}).items():
+                    if s.eval_kernel() in k.split("(")[0] and "hbm_bytes_per_launch" in v:
+                        traffic = v["hbm_bytes_per_launch"]
+        except (OSError, ValueError):
+            pass
 
     out = None
     if rank == 0:
-        if steps_done == args.steps and not converged:
+        if loop_rate:
             value, iters_s, ms_step, vkind = m * steps_done / dt, steps_done / dt, dt * 1e3 / steps_done, "loop"
         else:
             # converged before or during the timed region: no loop rate exists; report the
@@ -587,7 +651,6 @@ def main():
                                        f"clause-shard x{world}" if world > 1 else "one GPU")},
             "multi_gpu_plan": dict(mplan, chosen=plan, requested=args.plan) if world > 1 else None,
             "value_kind": vkind,
-            "trajectory_check": traj,
             "graphs": graphs,
             "graph_note": graph_note or None,
             "create_s_max_over_ranks": create_max,
@@ -595,6 +658,10 @@ def main():
             "violated_last": st["n_violated"],
             "avg_mis_size": st["avg_mis_size"],
             "lfmis_rounds_max": st["lfmis_rounds_max"],
+        }
+    if rank == 0 and args.full:
+        out.update({
+            "trajectory_check": traj,
             "phase_ms": {k2: pt[k2] for k2 in ("eval_ms", "exchange_ms", "mis_ms", "resample_ms", "total_ms")},
             "phase_iters": pt["iterations"],
             "phase_note": ("device wall-clock stamps per timed iteration: eval = evaluation kernel; "
@@ -630,7 +697,7 @@ def main():
                                  "GPU's bucketed round 0 fuses the round-0 scatter into it (k_eval_scatter)"),
                 "eval_ms_hip_events_eager_iterations": pe["eval_ms"] if pe else None,
             },
-        }
+        })
     s.close()
     run_done = __import__("threading").Event()  # (set once the line is out and the ranks are torn down)
     emitted = []
@@ -641,7 +708,7 @@ def main():
             result_out.write(json.dumps(o) + "\n")
             result_out.flush()
 
-    if world > 1 and plan == "replicate" and not args.no_shard_line:
+    if shard_too:
         # the clause-sharded path (exchange every iteration) on the same instance, so that a
         # multi-GPU run still exercises and checks it: its own rate and trajectory check
         # (a watchdog keeps the headline: if the sharded run and the teardown after it have not
@@ -666,7 +733,7 @@ def main():
         del offs, lits
         if rank == 0:
             out["shard_line"] = sh
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_rr_line:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_rr_line:
         # the CPU baseline runs the reference's -p T path, whose MIS is the T-set round robin
         # (SATInstance.h:414-447), not the one-set LFMIS timed above: the same workload with that
         # same MIS on the GPU, for a like-for-like ratio
@@ -674,14 +741,14 @@ def main():
             out["gpu_same_mis_as_cpu_baseline"] = rr_line_child(args)
         except Exception as e:  # reported, never fatal for the GPU number
             out["gpu_same_mis_as_cpu_baseline"] = {"value": None, "error": str(e)}
-    if rank == 0 and world == 1 and args.stream_line and args.stream_line != "none" and not args.rccl_self:
+    if args.full and rank == 0 and world == 1 and args.stream_line and args.stream_line != "none" and not args.rccl_self:
         try:
             st_T, st_b = (int(x) for x in args.stream_line.split(":"))
             n0, m0, k0, kind0, _ = CONFIGS[args.config]
             out["stream_line"] = stream_line(args, n0, m0, k0, kind0, st_T, st_b)
         except Exception as e:  # reported, never fatal for the GPU number
             out["stream_line"] = {"value": None, "error": str(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("[rank 0] cpu baseline: the reference's -p path on bounded samples")
         try:
             out["cpu_baseline"] = cpu_baseline(args.config, args.cpu_budget, args.cpu_full_iteration)

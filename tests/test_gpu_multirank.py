@@ -222,7 +222,7 @@ def test_bench_prints_one_json_line(mode):
     communicator; N=2 self-launched ranks over the host exchange on this one GPU).  With N=2 the
     planner replicates C2 and the sharded path runs as the checked secondary
     line; --plan shard makes the sharded path the headline."""
-    common = ["--config", "C2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--event-iters", "0"]
+    common = ["--full", "--config", "C2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--event-iters", "0"]
     if mode == "rccl_self":
         d = _bench_stdout(common + ["--rccl-self"])
         assert d["n_gpus"] == 1 and d["config"]["exchange"] == "allgather/rccl-self"
@@ -246,3 +246,36 @@ def test_bench_prints_one_json_line(mode):
             assert sl["trajectory_check"]["match"] is True, sl["trajectory_check"]
         assert d["trajectory_check"]["match"] is True, d["trajectory_check"]
     assert d["steps_done"] == 4 and d["value"] > 0
+
+
+def test_bench_plain_run_dumps_what_the_loop_computed(tmp_path):
+    """A plain run carries the headline alone (nothing of --full), times exactly --steps
+    iterations, and --dump-outputs writes the state the timed loop left: checked against the
+    committed oracle trajectory of C2 (tests/golden/bench_trajectory.json) after iteration
+    warmup + steps = 5.  At C2 every array is whole (no sample): n, m <= bench.DUMP_MAX_ELEMS."""
+    import json
+
+    from alllsatisfiabilitysolver_amd import assignment_digest
+
+    out = tmp_path / "outputs"
+    d = _bench_stdout(["--config", "C2", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out)])
+    n, m = 1_000_000, 4_000_000
+    assert d["steps"] == 4 and d["steps_done"] == 4 and d["value_kind"] == "loop" and d["graphs"] is True
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(m / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    assert d["unit"] == "clause-evals/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    for moved in ("trajectory_check", "phase_ms", "roofline", "gpu_same_mis_as_cpu_baseline", "stream_line",
+                  "cpu_baseline", "shard_line"):
+        assert moved not in d, moved
+    assert sorted(os.listdir(out)) == ["assignment.npy", "mis.npy", "stats.npy", "violated.npy"]
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64_000_000
+    a, mis, st, viol = (np.load(out / f"{q}.npy") for q in ("assignment", "mis", "stats", "violated"))
+    assert st.dtype == np.float64 and a.dtype == mis.dtype == viol.dtype == np.float32
+    assert a.shape == (n,) and mis.shape == (m,) and viol.shape == (m,)
+    rows = {r[0]: r for r in json.load(open(os.path.join(ROOT, "tests", "golden", "bench_trajectory.json")))
+            ["trajectories"]["C2_T1"]["rows"]}
+    _, nu, sum_mis, n_res, digest = rows[5]
+    assert st.tolist() == [5, n_res, sum_mis, sum_mis // 5, nu, 0]
+    assert set(np.unique(a)) <= {0.0, 1.0} and set(np.unique(viol)) <= {0.0, 1.0}
+    assert assignment_digest(np.packbits(a.astype(np.uint8), bitorder="little").view(np.uint32)) == digest
+    assert int(viol.sum()) == nu and int(mis.sum()) == sum_mis - rows[4][2]
+    assert not np.any((mis == 1) & (viol == 0))  # the MIS lies inside the violated set

@@ -8,7 +8,7 @@ T=${1:-n8}; CFGS=${2:-C4 C5}; S=${3:-3}; W=${4:-1}
 O=gpurun_out/$T
 mkdir -p $O
 for c in $CFGS; do
-  ALLL_BENCH_SAME_DEVICE=1 timeout -k 10 900 python bench.py --gpus 8 --config $c --exchange-impl host \
+  ALLL_BENCH_SAME_DEVICE=1 timeout -k 10 900 python bench.py --full --gpus 8 --config $c --exchange-impl host \
       --steps $S --warmup $W --no-cpu-baseline --event-iters 0 > $O/bench_${c}_n8host.json 2> $O/bench_${c}_n8host.err
   rc=$?; echo "$c rc=$rc"; tail -3 $O/bench_${c}_n8host.err
   case $rc in 0) ;; *) exit $rc;; esac

@@ -12,7 +12,7 @@ for pmc in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "TD_TD_BUSY_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum"; do
   i=$((i+1))
   timeout -s KILL 120 rocprofv3 --pmc $pmc --kernel-include-regex "k_eval" --output-format csv -d $OUT/p$i -o run -- \
-      python3 bench.py --no-cpu-baseline --steps 10 --warmup 2 --event-iters 0 > $OUT/b$i.json 2> $OUT/b$i.err
+      python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 2 --event-iters 0 > $OUT/b$i.json 2> $OUT/b$i.err
   rc=$?; [ $rc -eq 0 ] || { echo "pass $i rc=$rc"; tail -3 $OUT/b$i.err; }
 done
 python3 tools/pmc_table.py $OUT > $OUT/table.txt; cat $OUT/table.txt

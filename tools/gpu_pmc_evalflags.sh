@@ -17,7 +17,7 @@ for pmc in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
       python3 tools/rr_bench.py --config M --threads 16 --iters 2 --warmup 20 > $OUT/rr$i.log 2>&1 \
       || { echo "rr pass $i rc=$?"; tail -3 $OUT/rr$i.log; exit 1; }
   timeout -s KILL 150 rocprofv3 --pmc $pmc --kernel-include-regex "k_eval" --output-format csv -d $OUT/t1_$i -o run -- \
-      python3 bench.py --no-cpu-baseline --stream-line none --no-shard-line --steps 10 --warmup 2 > $OUT/t1_$i.log 2>&1 \
+      python3 bench.py --full --no-cpu-baseline --stream-line none --no-shard-line --steps 10 --warmup 2 > $OUT/t1_$i.log 2>&1 \
       || { echo "t1 pass $i rc=$?"; tail -3 $OUT/t1_$i.log; exit 1; }
 done
 python3 - "$OUT" <<'PY'

@@ -14,7 +14,7 @@ for pmc in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
   timeout -s KILL 150 rocprofv3 --pmc $pmc --kernel-include-regex "$REGEX" --output-format csv -d $OUT/p$i -o run -- \
-      python3 bench.py --config $CFG --no-cpu-baseline --steps 10 --warmup 2 --event-iters 0 \
+      python3 bench.py --full --config $CFG --no-cpu-baseline --steps 10 --warmup 2 --event-iters 0 \
       > $OUT/b$i.json 2> $OUT/b$i.err
   rc=$?
   if [ $rc -ne 0 ]; then echo "pmc pass $i ($pmc) failed rc=$rc"; tail -5 $OUT/b$i.err; exit $rc; fi

@@ -10,7 +10,7 @@ if [ -n "$1" ]; then
   rc=$?; echo "pytest rc=$rc"; tail -4 gpurun_out/pytest_$TAG.log; [ $rc -eq 0 ] || exit $rc
 fi
 for c in $2; do
-  timeout -k 10 300 python bench.py --config $c --no-cpu-baseline --steps 40 --warmup 5 --event-iters 0 \
+  timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline --steps 40 --warmup 5 --event-iters 0 \
       > gpurun_out/bench_${TAG}_$c.json 2> gpurun_out/bench_${TAG}_$c.err
   rc=$?; [ $rc -eq 0 ] || { echo "bench $c rc=$rc"; tail -5 gpurun_out/bench_${TAG}_$c.err; exit $rc; }
   python3 -c "

@@ -16,5 +16,5 @@ timeout -k 10 300 python tools/rr_bench.py --config M --threads 16,4 --warmup 20
 rc=$?; cat $O/rr_M.json; fatal $rc rrM
 timeout -k 10 300 python tools/rr_bench.py --config C2 --threads 16 --warmup 20 --iters 20 > $O/rr_C2.json 2> $O/rr_C2.err
 rc=$?; cat $O/rr_C2.json; fatal $rc rrC2
-timeout -k 10 400 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 rc=$?; tail -2 $O/bench.err; python tools/bench_brief.py $O/bench.json; fatal $rc bench
