@@ -1,5 +1,6 @@
-// alll_internal.h -- shared between the HIP kernels (alll_kernels.hip) and the host runtime
-// (alll_runtime.cpp).  Not part of the public ABI.
+// alll_internal.h -- shared between the HIP kernels (alll_kernels.hip, alll_stream.hip,
+// alll_refrng.hip), the host runtime (alll_runtime.cpp) and its host-only layout planner
+// (alll_layout.cpp).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -17,13 +17,12 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
-#include <sched.h>
-#include <thread>
 #include <string>
 #include <vector>
 
 #include "alll.h"
 #include "alll_internal.h"
+#include "alll_layout.h"
 
 using namespace alll;
 
@@ -60,7 +59,6 @@ constexpr uint32_t DEFAULT_GRID_ROUNDS = 4;
 // captured graphs of 1, 2, 4 and 8 iterations: a batch of n iterations replays n / 8 eight-
 // iteration graphs and at most one of each smaller size (one launch gap per graph)
 constexpr int GRAPH_SIZES = 4;
-constexpr uint64_t SMALL_U_DEFAULT = 8192;
 constexpr uint32_t GRAPH_UNROLL = 1u << (GRAPH_SIZES - 1);
 constexpr uint32_t SKEWED_GRID_ROUNDS = 7;  // instances with hot variables
 
@@ -82,7 +80,6 @@ struct alll_ctx {
     // evaluation alone keeps its own kernel (k_eval_hybrid<K>: alll_bench_eval, verify, the
     // other variants) for its roofline.  env ALLL_FUSE_SCATTER=0: the separate k_bscatter
     bool fuse_scatter = true;
-    std::vector<uint32_t> run_t0;  // bucketed round 0: first tile of every run (+ end)
     int rank = 0, world = 1;
     bool allreduce = false;
     ncclComm_t comm = nullptr;
@@ -143,58 +140,6 @@ struct alll_ctx {
 
 namespace {
 
-// Host threads for the layout work of alll_create: the process's CPU affinity, at most 16
-// (the CPU share of one GPU on the MI355X boxes) or OMP_NUM_THREADS when set.
-unsigned host_threads() {
-    unsigned n = std::max(1u, std::thread::hardware_concurrency());
-    cpu_set_t cs;
-    if (sched_getaffinity(0, sizeof cs, &cs) == 0) n = std::max(1, CPU_COUNT(&cs));
-    unsigned cap = 16;
-    if (const char* e = getenv("OMP_NUM_THREADS")) { const int v = atoi(e); if (v > 0) cap = (unsigned)v; }
-    return std::min(n, cap);
-}
-
-// Runs f(i) for i in [0, n) on up to nt threads (contiguous blocks of indices).
-template <typename F>
-void parallel_for(uint64_t n, unsigned nt, F f) {
-    nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nt, n / 4096 + 1));
-    if (nt <= 1) { for (uint64_t i = 0; i < n; ++i) f(i); return; }
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; ++t)
-        th.emplace_back([&, t] { for (uint64_t i = n * t / nt; i < n * (t + 1) / nt; ++i) f(i); });
-    for (auto& x : th) x.join();
-}
-
-// f(t, begin, end) on up to nt threads over contiguous blocks of [0, n); returns the threads used
-template <typename F>
-unsigned parallel_chunks(uint64_t n, unsigned nt, F f) {
-    nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nt, n / 65536 + 1));
-    if (nt <= 1) { f(0u, (uint64_t)0, n); return 1; }
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; ++t) th.emplace_back([&, t] { f(t, n * t / nt, n * (t + 1) / nt); });
-    for (auto& x : th) x.join();
-    return nt;
-}
-
-// std::sort of a[0, n) on nt threads: sorted blocks, then pairwise merges level by level.
-template <typename T, typename Cmp>
-void parallel_sort(T* a, size_t n, Cmp cmp, unsigned nt) {
-    if (nt <= 1 || n < (1u << 16)) { std::sort(a, a + n, cmp); return; }
-    std::vector<size_t> cut(nt + 1);
-    for (unsigned i = 0; i <= nt; ++i) cut[i] = n * i / nt;
-    {
-        std::vector<std::thread> th;
-        for (unsigned i = 0; i < nt; ++i) th.emplace_back([&, i] { std::sort(a + cut[i], a + cut[i + 1], cmp); });
-        for (auto& x : th) x.join();
-    }
-    for (unsigned w = 1; w < nt; w *= 2) {
-        std::vector<std::thread> th;
-        for (unsigned i = 0; i + w < nt; i += 2 * w)
-            th.emplace_back([&, i, w] { std::inplace_merge(a + cut[i], a + cut[i + w], a + cut[std::min(i + 2 * w, nt)], cmp); });
-        for (auto& x : th) x.join();
-    }
-}
-
 template <typename T>
 int dalloc(alll_ctx* c, T** p, size_t count, int fill = 0) {
     size_t bytes = std::max<size_t>(count * sizeof(T), 16);
@@ -209,107 +154,15 @@ int dalloc(alll_ctx* c, T** p, size_t count, int fill = 0) {
     return ALLL_OK;
 }
 
-// Ragged-width evaluation layout (ClauseView::rg_off, k_eval_ragged): inside every shard the
-// clauses are evaluated sorted by (width, block of the smallest variable, largest variable),
-// so a chunk's 256 clauses share one width and the slot-0 lookups of a wave fall on few
-// lines; every clause's literals are stored by descending variable (its smallest variable,
-// looked up last, lies in the tile's LDS window) and padded to its chunk's width with an
-// always-false literal.  perm maps positions to clause ids (CLAIM(0) translates the
-// evaluation's positions; alll_get_violated_mask reorders the bitmask on the host).
-int build_ragged(alll_ctx* c, const alll_problem* prob) {
-    const uint64_t m = c->m;
-    const uint64_t* offs = prob->offsets;
-    const uint32_t* lits = prob->literals;
-    LoopBuffers& b = c->b;
-    ClauseView& cv = c->cv;
-    const uint64_t win_vars = (uint64_t)b.win_words * 32;
-    bool windows = c->n_vars > win_vars;
-    if (const char* e = getenv("ALLL_EVAL_WINDOWS")) windows = atoi(e) != 0;
-    const unsigned nt = host_threads();
-    std::vector<uint32_t>& perm = c->perm;
-    perm.resize(m);
-    struct Key { uint64_t k1; uint32_t id; };
-    auto key_of = [&](uint64_t cl) -> Key {
-        uint32_t hi = 0, lo = ~0u;
-        for (uint64_t j = offs[cl]; j < offs[cl + 1]; ++j) {
-            const uint32_t v = lits[j] >> 1;
-            hi = std::max(hi, v);
-            lo = std::min(lo, v);
-        }
-        const uint64_t w = std::min<uint64_t>(offs[cl + 1] - offs[cl], (1u << 20) - 1);
-        const uint64_t blk = (windows && lo != ~0u) ? std::min<uint64_t>(lo / win_vars, 1023) : 0;
-        return {(w << 40) | (blk << 30) | (hi & ((1u << 30) - 1)), (uint32_t)cl};
-    };
-    // the own shard only (a clause range; the other ranks' shards keep clause order here: their
-    // lists come from the all-gathered clause-order mask, k_collect)
-    parallel_for(m, nt, [&](uint64_t i) { perm[i] = (uint32_t)i; });
-    {
-        const uint64_t cb0 = std::min<uint64_t>(m, (uint64_t)c->own_begin * TILE);
-        const uint64_t ce0 = std::min<uint64_t>(m, (uint64_t)c->own_end * TILE);
-        std::vector<Key> kv(ce0 - cb0);
-        parallel_for(ce0 - cb0, nt, [&](uint64_t i) { kv[i] = key_of(cb0 + i); });
-        parallel_sort(kv.data(), kv.size(), [](const Key& x, const Key& y) {
-            return x.k1 != y.k1 ? x.k1 < y.k1 : x.id < y.id;
-        }, nt);
-        parallel_for(kv.size(), nt, [&](uint64_t i) { perm[cb0 + i] = kv[i].id; });
-    }
-    // chunk widths and offsets (units of CHUNK words)
-    const uint64_t n_chunks = (m + CHUNK - 1) / CHUNK;
-    std::vector<uint32_t> off(n_chunks + 1, 0u);
-    uint64_t acc = 0;
-    for (uint64_t g = 0; g < n_chunks; ++g) {
-        uint64_t w = 0;
-        for (uint64_t p = g * CHUNK; p < std::min<uint64_t>(m, (g + 1) * CHUNK); ++p)
-            w = std::max<uint64_t>(w, offs[perm[p] + 1] - offs[perm[p]]);
-        off[g] = (uint32_t)acc;
-        acc += w;
-        if (acc >= (1ull << 32)) return fail(ALLL_ERR_UNSUPPORTED, "ragged layout exceeds 2^32 chunk slots");
-    }
-    off[n_chunks] = (uint32_t)acc;
-    static_assert(sizeof(b.n_words) == 4, "n_words");
-    if (b.n_words >= (1u << 25)) return fail(ALLL_ERR_UNSUPPORTED, "ragged layout needs n_words < 2^25");
-    const uint32_t false_lit = 64u * b.n_words;  // variable 32 * n_words: its word is out of range
-    std::vector<uint32_t> t((size_t)acc * CHUNK, false_lit);
-    const uint64_t own_p0 = std::min<uint64_t>(m, (uint64_t)c->own_begin * TILE);
-    const uint64_t own_p1 = std::min<uint64_t>(m, (uint64_t)c->own_end * TILE);
-    parallel_for(own_p1 - own_p0, nt, [&](uint64_t q) {
-        const uint64_t p = own_p0 + q;
-        const uint64_t cl = perm[p], g = p / CHUNK, r = p % CHUNK;
-        const uint64_t w = offs[cl + 1] - offs[cl];
-        std::vector<uint32_t> tmp(lits + offs[cl], lits + offs[cl] + w);
-        std::sort(tmp.begin(), tmp.end(), [](uint32_t x, uint32_t y) { return (x >> 1) > (y >> 1); });
-        uint32_t* dst = t.data() + (size_t)off[g] * CHUNK + r;
-        for (uint64_t j = 0; j < w; ++j) dst[j * CHUNK] = tmp[j];
-    });
-    uint32_t *d_off = nullptr, *d_lits = nullptr, *d_perm = nullptr, *d_wb = nullptr;
-    int rc;
-    if ((rc = dalloc(c, &d_off, n_chunks + 1)) || (rc = dalloc(c, &d_lits, t.size())) || (rc = dalloc(c, &d_perm, m)))
-        return rc;
-    std::vector<uint32_t> wb;
-    if (windows) {
-        const uint32_t lds_words = std::min<uint32_t>(b.n_words, b.win_words);
-        wb.assign(b.n_tiles, 0u);
-        for (uint32_t tt = c->own_begin; tt < c->own_end; ++tt) {
-            const uint64_t p = (uint64_t)tt * TILE;
-            if (p >= m) break;
-            const uint64_t cl = perm[p];
-            uint32_t lo = ~0u;
-            for (uint64_t j = offs[cl]; j < offs[cl + 1]; ++j) lo = std::min(lo, lits[j] >> 1);
-            if (lo == ~0u) lo = 0;
-            wb[tt] = std::min<uint64_t>((uint64_t)(lo / win_vars) * b.win_words, b.n_words - lds_words);
-        }
-        if ((rc = dalloc(c, &d_wb, b.n_tiles))) return rc;
-    }
+// dalloc, then v's contents once the zero-fill has drained (`what` names it in the failure text)
+template <typename T, typename P>
+int upload(alll_ctx* c, P** p, const std::vector<T>& v, const char* what) {
+    T* d = nullptr;
+    if (int rc = dalloc(c, &d, v.size())) return rc;
     if (hipStreamSynchronize(c->stream) != hipSuccess ||
-        hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (!t.empty() && hipMemcpy(d_lits, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(d_perm, perm.data(), m * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (d_wb && hipMemcpy(d_wb, wb.data(), wb.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
-        return fail(ALLL_ERR_HIP, "ragged layout upload failed");
-    cv.rg_off = d_off;
-    cv.rg_lits = d_lits;
-    cv.perm = d_perm;
-    if (d_wb) b.win_base = d_wb;
+        (!v.empty() && hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess))
+        return fail(ALLL_ERR_HIP, "%s upload failed", what);
+    *p = d;
     return ALLL_OK;
 }
 
@@ -884,171 +737,12 @@ int alll_comm_unique_id(uint8_t out[128]) {
     return ALLL_OK;
 }
 
-int alll_create(const alll_problem* prob, const alll_options* opt_in, alll_ctx** out) {
-    if (!prob || !out) return fail(ALLL_ERR_INVALID_ARG, "null argument");
-    *out = nullptr;
-    alll_options opt;
-    if (opt_in) opt = *opt_in; else alll_default_options(&opt);
-    if (opt.world < 1 || opt.rank < 0 || opt.rank >= opt.world)
-        return fail(ALLL_ERR_INVALID_ARG, "bad rank %d / world %d", opt.rank, opt.world);
-    if (opt.world > ALLL_MAX_GPU_STATS) return fail(ALLL_ERR_UNSUPPORTED, "world > %d", ALLL_MAX_GPU_STATS);
-    const uint64_t m = prob->n_clauses;
-    if (m && (!prob->offsets)) return fail(ALLL_ERR_INVALID_ARG, "null offsets");
-    if (m >= 0xFFFFFFFFull - TILE) return fail(ALLL_ERR_UNSUPPORTED, "more than 2^32-4097 clauses");
-    // ---- validate the CSR on the host (the reference has UB here: Clause.h:40)
-    const uint64_t L = m ? prob->offsets[m] : 0;
-    if (m && prob->offsets[0] != 0) return fail(ALLL_ERR_BAD_INPUT, "offsets[0] != 0");
-    if (L && !prob->literals) return fail(ALLL_ERR_INVALID_ARG, "null literals");
-    if (L >= 0xFFFFFFFFull) return fail(ALLL_ERR_UNSUPPORTED, "more than 2^32-1 literals");
-    // (host passes over the instance run on the process's threads: at 128M clauses / 384M
-    // literals a serial pass costs ~0.5 s, and every rank of a sharded run makes them)
-    const unsigned hnt = host_threads();
-    int fixed_k = -1;
-    if (m) {
-        const uint64_t w0 = prob->offsets[1] - prob->offsets[0];
-        std::vector<uint64_t> bad(hnt, ~0ull);
-        std::vector<uint8_t> ragged(hnt, 0);
-        parallel_chunks(m, hnt, [&](unsigned t, uint64_t c0, uint64_t c1) {
-            for (uint64_t c = c0; c < c1; ++c) {
-                if (prob->offsets[c + 1] < prob->offsets[c]) { bad[t] = c; return; }
-                if (prob->offsets[c + 1] - prob->offsets[c] != w0) ragged[t] = 1;
-            }
-        });
-        const uint64_t first_bad = *std::min_element(bad.begin(), bad.end());
-        if (first_bad != ~0ull) return fail(ALLL_ERR_BAD_INPUT, "offsets decrease at %llu", (unsigned long long)first_bad);
-        fixed_k = *std::max_element(ragged.begin(), ragged.end()) ? 0 : (int)std::min<uint64_t>(w0, 1 << 30);
-    }
-    // the streaming solve keeps the clause-order (CSR) layout: its window rule needs the first
-    // violated clause index, read from a clause-order bitmask
-    // the round-robin MIS of T > 1 chunks (the reference's n_threads > 1) walks clause-order
-    // lists of violated clauses: fixed widths keep the hybrid evaluation, whose lists are turned
-    // into clause-order flags (k_rr_mark); ragged widths the CSR evaluation
-    const uint32_t rr_T = (opt.n_threads > 1 && !(opt.flags & ALLL_FLAG_LFMIS) && !opt.stream_batch)
-                              ? (uint32_t)opt.n_threads : 0u;
-    if (rr_T > RR_TMAX) return fail(ALLL_ERR_UNSUPPORTED, "n_threads %u > %u chunks", rr_T, RR_TMAX);
-    // the streaming solve with n_threads > 1: T clause generators and the per-batch round robin
-    // (SATInstance.h:70-153)
-    const uint32_t srr_T = (opt.n_threads > 1 && !(opt.flags & ALLL_FLAG_LFMIS) && opt.stream_batch)
-                               ? (uint32_t)opt.n_threads : 0u;
-    if (srr_T) {
-        if (srr_T > RR_TMAX) return fail(ALLL_ERR_UNSUPPORTED, "streaming solve: n_threads %u > %u", srr_T, RR_TMAX);
-        if (opt.world > 1) return fail(ALLL_ERR_UNSUPPORTED, "streaming solve with n_threads > 1 runs on one GPU");
-        // an empty clause is violated forever and, sharing no variable, joins the MIS at every batch
-        // step; the reference never returns on it (as with one thread), and here its repeats past the
-        // materialised steps would be miscounted: refused
-        for (uint64_t c = 0; c < m; ++c)
-            if (prob->offsets[c + 1] == prob->offsets[c])
-                return fail(ALLL_ERR_UNSUPPORTED, "streaming solve with n_threads > 1: clause %llu is empty",
-                            (unsigned long long)c);
-    }
-    // the reference's own random stream (ALLL_FLAG_REFERENCE_RNG, alll_refrng.hip): defined for the
-    // one-thread loop on one GPU (the reference's T > 1 resample draws from T engines inside a
-    // schedule(dynamic) loop, so its bits follow the thread timing)
-    const bool refrng = (opt.flags & ALLL_FLAG_REFERENCE_RNG) != 0;
-    if (refrng) {
-        bool zid = true;
-        for (int i = 0; i < 128; ++i) zid &= opt.comm_id[i] == 0;
-        if (opt.n_threads > 1)
-            return fail(ALLL_ERR_UNSUPPORTED, "reference-RNG mode: n_threads must be 1 (the reference's T > 1 "
-                                              "resample draws from T engines in a schedule(dynamic) loop)");
+namespace {
 
-        if (opt.world > 1 || !zid || (opt.flags & ALLL_FLAG_EXCHANGE_ALLREDUCE))
-            return fail(ALLL_ERR_UNSUPPORTED, "reference-RNG mode runs on one GPU without the exchange path");
-    }
-    std::vector<uint32_t> rr_sets;
-    if (rr_T) {
-        rr_sets.resize(rr_T + 1);
-        if (opt.set_starts) {
-            if (opt.set_starts[0] != 0 || opt.set_starts[rr_T] != m)
-                return fail(ALLL_ERR_INVALID_ARG, "set_starts must run from 0 to n_clauses");
-            for (uint32_t q = 0; q <= rr_T; ++q) {
-                if (q && opt.set_starts[q] < opt.set_starts[q - 1])
-                    return fail(ALLL_ERR_INVALID_ARG, "set_starts decrease at %u", q);
-                rr_sets[q] = (uint32_t)opt.set_starts[q];
-            }
-        } else {
-            // example/main.cpp:149-178: chunk_size = ceil(m / T); clause c moves to the next
-            // chunk when c > (t + 1) * chunk_size, so chunk q >= 1 starts at q * chunk_size + 1
-            const uint64_t chunk = (m + rr_T - 1) / rr_T;
-            rr_sets[0] = 0;
-            for (uint32_t q = 1; q <= rr_T; ++q) rr_sets[q] = (uint32_t)std::min<uint64_t>(m, q * chunk + 1);
-            rr_sets[rr_T] = (uint32_t)m;
-        }
-    }
-    const int rr_width = fixed_k;  // common clause width (-1: no clauses, 0: ragged)
-    if (fixed_k < 1 || fixed_k > MAX_FIXED_K || (opt.flags & ALLL_FLAG_GENERIC_CSR) || opt.stream_batch)
-        fixed_k = 0;
-    const uint64_t lim = 2ull * prob->n_vars;
-    {
-        std::vector<uint64_t> bad(hnt, ~0ull);
-        parallel_chunks(L, hnt, [&](unsigned t, uint64_t j0, uint64_t j1) {
-            for (uint64_t j = j0; j < j1; ++j)
-                if (prob->literals[j] >= lim) { bad[t] = j; return; }
-        });
-        const uint64_t j = *std::min_element(bad.begin(), bad.end());
-        if (j != ~0ull)
-            return fail(ALLL_ERR_LITERAL_RANGE, "literal %u at position %llu exceeds n_vars %u",
-                        prob->literals[j], (unsigned long long)j, prob->n_vars);
-    }
+// ---- alll_create's steps: alll_layout.cpp plans what the buffers hold; the functions below
+// allocate and upload it (the order of the allocations is kept: device addresses follow from it)
 
-    // ---- hot variables (skewed degree: power-law hubs): degree >= max(1024, 32 x mean degree),
-    // at most HOT_MAX of the highest; flagged in bit 31 of every literal copy the device uses
-    std::vector<uint8_t> is_hot;
-    uint32_t n_hot = 0;
-    if (L && prob->n_vars && prob->n_vars < (1u << 30)) {
-        // degrees from per-thread 16-bit saturating histograms (4-5x faster than shared atomic
-        // counters at 384M literals), exact recount for the rare saturated candidates
-        const uint64_t thr = std::max<uint64_t>(HOT_THR_MIN, HOT_MEAN_X * (L / prob->n_vars + 1));
-        const unsigned dnt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(hnt, (2ull << 30) / (2ull * prob->n_vars)));
-        std::vector<std::vector<uint16_t>> hist(dnt);
-        const unsigned used = parallel_chunks(L, dnt, [&](unsigned t, uint64_t j0, uint64_t j1) {
-            std::vector<uint16_t>& h = hist[t];
-            h.assign(prob->n_vars, 0);
-            for (uint64_t j = j0; j < j1; ++j) {
-                uint16_t& c = h[prob->literals[j] >> 1];
-                c += c != 0xFFFF;
-            }
-        });
-        std::vector<std::vector<std::pair<uint32_t, uint32_t>>> hot_t(hnt);
-        std::vector<std::vector<uint32_t>> rec_t(hnt);
-        parallel_chunks(prob->n_vars, hnt, [&](unsigned t, uint64_t v0, uint64_t v1) {
-            for (uint64_t v = v0; v < v1; ++v) {
-                uint64_t d = 0;
-                bool sat = false;
-                for (unsigned q = 0; q < used; ++q) { d += hist[q][v]; sat |= hist[q][v] == 0xFFFF; }
-                // (a saturated count is a lower bound: such a variable is recounted exactly
-                // whatever its sum, the threshold applies to exact sums only)
-                if (sat) rec_t[t].push_back((uint32_t)v);
-                else if (d >= thr) hot_t[t].push_back({(uint32_t)d, (uint32_t)v});
-            }
-        });
-        hist.clear();
-        std::vector<std::pair<uint32_t, uint32_t>> hot;
-        std::vector<uint32_t> recount;  // (ascending: the chunks are in variable order)
-        for (unsigned t = 0; t < hnt; ++t) {
-            hot.insert(hot.end(), hot_t[t].begin(), hot_t[t].end());
-            recount.insert(recount.end(), rec_t[t].begin(), rec_t[t].end());
-        }
-        if (!recount.empty()) {  // (a variable with >= 65535 literals in one thread's range)
-            std::vector<uint64_t> d(recount.size(), 0);
-            for (uint64_t j = 0; j < L; ++j) {
-                const uint32_t v = prob->literals[j] >> 1;
-                const auto it = std::lower_bound(recount.begin(), recount.end(), v);
-                if (it != recount.end() && *it == v) ++d[it - recount.begin()];
-            }
-            for (size_t q = 0; q < recount.size(); ++q)
-                if (d[q] >= thr) hot.push_back({(uint32_t)std::min<uint64_t>(d[q], 0xFFFFFFFFu), recount[q]});
-        }
-        if (!hot.empty()) {
-            std::sort(hot.rbegin(), hot.rend());
-            if (hot.size() > HOT_MAX) hot.resize(HOT_MAX);
-            is_hot.assign(prob->n_vars, 0);
-            for (auto& h : hot) is_hot[h.second] = 1;
-            n_hot = (uint32_t)hot.size();
-        }
-    }
-
-    // ---- device
+int open_device(const alll_options& opt, alll_ctx** pc) {
     int ndev = alll_device_count();
     if (ndev <= 0) return fail(ALLL_ERR_NO_DEVICE, "no HIP device visible");
     int dev = opt.device;
@@ -1060,24 +754,12 @@ int alll_create(const alll_problem* prob, const alll_options* opt_in, alll_ctx**
     alll_ctx* c = new (std::nothrow) alll_ctx();
     if (!c) return fail(ALLL_ERR_OOM, "host allocation failed");
     c->device = dev;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            c->n_cu = prop.multiProcessorCount;
-    }
-    c->opt = opt;
-    c->n_vars = prob->n_vars;
-    c->m = m;
-    c->n_lits = L;
-    c->rank = opt.rank;
-    c->world = opt.world;
-    c->allreduce = (opt.flags & ALLL_FLAG_EXCHANGE_ALLREDUCE) != 0;
-    c->use_graph = (opt.flags & ALLL_FLAG_NO_GRAPH) == 0;
-    if (!c->use_graph) c->graph_note = "ALLL_FLAG_NO_GRAPH";
-    c->grid_rounds = opt.grid_rounds ? opt.grid_rounds : DEFAULT_GRID_ROUNDS;
-    c->small_u = SMALL_U_DEFAULT;
-    if (const char* e = getenv("ALLL_SMALL_U")) c->small_u = strtoull(e, nullptr, 10);  // tuning, tests
-    if (const char* e = getenv("ALLL_FUSE_SCATTER")) c->fuse_scatter = atoi(e) != 0;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+        c->n_cu = prop.multiProcessorCount;
+    int khz = 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0)
+        c->wall_khz = khz;
     auto bail = [&](int rc) { alll_destroy(c); return rc; };
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
         return bail(fail(ALLL_ERR_HIP, "hipStreamCreate failed"));
@@ -1088,534 +770,289 @@ int alll_create(const alll_problem* prob, const alll_options* opt_in, alll_ctx**
         return bail(fail(ALLL_ERR_OOM, "hipHostMalloc failed"));
     if (hipEventCreateWithFlags(&c->ev_async, hipEventDisableTiming) != hipSuccess)
         return bail(fail(ALLL_ERR_HIP, "hipEventCreate failed"));
+    *pc = c;
+    return ALLL_OK;
+}
 
-    // ---- tiles and shards (contiguous clause ranges; concatenation = clause order)
-    const uint32_t n_tiles = (uint32_t)((m + TILE - 1) / TILE);
-    c->tiles_per_rank = (n_tiles + c->world - 1) / c->world;
-    if (c->tiles_per_rank == 0) c->tiles_per_rank = 1;
-    c->n_tiles_padded = c->tiles_per_rank * c->world;
-    c->own_begin = std::min<uint32_t>(n_tiles, (uint32_t)c->rank * c->tiles_per_rank);
-    c->own_end = std::min<uint32_t>(n_tiles, c->own_begin + c->tiles_per_rank);
-    c->b.own_begin = c->own_begin;
-    c->b.own_end = c->own_end;
+// the context's scalar fields; the loop buffers and the clause view start from the planned ones
+void set_shape(alll_ctx* c, const alll_options& opt, const Knobs& kn, const Layout& l) {
+    c->opt = opt;
+    c->n_vars = l.n_vars;
+    c->m = l.m;
+    c->n_lits = l.n_lits;
+    c->rank = opt.rank;
+    c->world = opt.world;
+    c->allreduce = (opt.flags & ALLL_FLAG_EXCHANGE_ALLREDUCE) != 0;
+    c->use_graph = (opt.flags & ALLL_FLAG_NO_GRAPH) == 0;
+    if (!c->use_graph) c->graph_note = "ALLL_FLAG_NO_GRAPH";
+    // skewed instances need more rounds before the leftovers are few enough for the
+    // single-workgroup tail (power-law 3-SAT at 10M clauses: 10 rounds)
+    c->grid_rounds = opt.grid_rounds ? opt.grid_rounds : (l.cv.n_hot ? SKEWED_GRID_ROUNDS : DEFAULT_GRID_ROUNDS);
+    c->small_u = kn.small_u;
+    c->fuse_scatter = kn.fuse_scatter;
+    c->tiles_per_rank = l.tiles_per_rank;
+    c->n_tiles_padded = l.n_tiles_padded;
+    c->own_begin = l.b.own_begin;
+    c->own_end = l.b.own_end;
+    c->b = l.b;  // (the planned scalars; every pointer still null)
+    c->cv = l.cv;
+}
 
-    int rc;
+// the round robin of T > 1 chunks: scan entries, the batch kernel (fallback of the fixpoint),
+// the fixpoint passes and the incremental passes (§4.3.3)
+int alloc_round_robin(alll_ctx* c, const Layout& l) {
+    if (!l.b.rr_T) return ALLL_OK;
     LoopBuffers& b = c->b;
-    b.n_vars = c->n_vars;
-    b.n_words = (c->n_vars + 31) / 32;
-    b.win_words = LDS_WORDS;
-    if (const char* e = getenv("ALLL_WIN_WORDS"))  // tests: small windows on small instances
-        b.win_words = std::max<uint32_t>(16, std::min<uint32_t>(b.win_words, (uint32_t)std::max(0, atoi(e)))) / 8 * 8;
-    b.n_cu = (uint32_t)c->n_cu;
-    b.n_tiles = n_tiles;
-    b.m = m;
-    if (opt.stream_batch && m && !srr_T) {
-        // key of the streaming solve: position in the generator sequence j*P mod m, so the
-        // inverse of P mod m (P is prime, so it exists for every m < P)
-        const uint64_t p = 9223372036854775783ull % m;
-        int64_t r0 = (int64_t)m, r1 = (int64_t)p, t0 = 0, t1 = 1;
-        while (r1) {
-            const int64_t q = r0 / r1;
-            int64_t x = r0 - q * r1; r0 = r1; r1 = x;
-            x = t0 - q * t1; t0 = t1; t1 = x;
-        }
-        if (m > 1 && r0 != 1) return bail(fail(ALLL_ERR_UNSUPPORTED, "generator step not invertible mod %llu",
-                                                (unsigned long long)m));
-        b.stream_pinv = m > 1 ? (uint64_t)((t0 % (int64_t)m + (int64_t)m) % (int64_t)m) : 0;
-        b.stream_batch = opt.stream_batch;
+    const uint64_t m = l.m, L = l.n_lits;
+    const size_t nv = l.n_vars;
+    const uint32_t T = l.b.rr_T;
+    int rc;
+    if ((rc = dalloc(c, &b.rr_u, 12 * (size_t)m))) return rc;  // scan entries (k_rr_entries)
+    if (l.fixed_k > 0) {  // the hybrid evaluation's lists -> clause-order flags (k_rr_mark)
+        if ((rc = dalloc(c, &b.rr_flag, (size_t)l.b.n_tiles * TILE)) || (rc = dalloc(c, &b.rr_tcnt, l.b.n_tiles))) return rc;
     }
-    b.seed = opt.seed;
-    if (rr_T) {
-        uint32_t* d_sets = nullptr;
-        if ((rc = dalloc(c, &b.rr_u, 12 * (size_t)m))) return bail(rc);  // scan entries (k_rr_entries)
-        if (fixed_k > 0) {  // the hybrid evaluation's lists -> clause-order flags (k_rr_mark)
-            if ((rc = dalloc(c, &b.rr_flag, (size_t)n_tiles * TILE))) return bail(rc);
-            if ((rc = dalloc(c, &b.rr_tcnt, n_tiles))) return bail(rc);
-        }
-        if ((rc = dalloc(c, &d_sets, rr_T + 1))) return bail(rc);
-        if (hipStreamSynchronize(c->stream) != hipSuccess ||
-            hipMemcpy(d_sets, rr_sets.data(), (rr_T + 1) * 4ull, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(ALLL_ERR_HIP, "chunk upload failed"));
-        b.rr_sets = d_sets;
-        b.rr_T = rr_T;
-        b.rr_k = (rr_width >= 1 && rr_width <= 8) ? (uint32_t)rr_width : 0u;
-        // the batch kernel (fallback of the fixpoint): one workgroup per lane group, at most 64
-        const uint32_t mw = std::min<uint32_t>(rr_T, 64);
-        if ((rc = dalloc(c, &b.rr_ctl, RR_MW_CTL_WORDS))) return bail(rc);
-        if ((rc = dalloc(c, &b.rr_gkey, RR_MW_GH))) return bail(rc);
-        if ((rc = dalloc(c, &b.rr_gmin, RR_MW_GH, 0xFF))) return bail(rc);
-        if ((rc = dalloc(c, &b.rr_ptr, rr_T))) return bail(rc);
-        if ((rc = dalloc(c, &b.rr_end, rr_T))) return bail(rc);
-        b.rr_mw = mw;
-        // the fixpoint passes: keys {epoch | turn | entry} need >= 10 epoch
-        // bits; ALLL_RR_FP=0 leaves every iteration to the batch kernels, ALLL_RR_FP_MAX sets the
-        // passes per iteration (graph unroll)
-        auto bits_of = [](uint64_t x) { uint32_t k = 1; while (k < 64 && (x >> k)) ++k; return k; };
-        const uint32_t ib = bits_of(m), tb = bits_of(m + rr_T + 1);
-        bool fp = rr_T <= FP_TMAX && ib + tb + 10 <= 64 && ib <= 28;  // (28: the claim pairs' slot tags)
-        if (const char* e = getenv("ALLL_RR_FP")) fp = fp && atoi(e) != 0;
-        if (fp) {
-            const size_t nblk = m / FP_B + 2;
-            if ((rc = dalloc(c, &b.fp_ctl, 1))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_in, m + FP_B))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_turn, m + 1))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_v4, (rr_width >= 1 && rr_width <= 4) ? m + 1 : 1))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_sole, (size_t)m * ((rr_width >= 1 && rr_width <= 4) ? 4 : 8) + 16))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_list, 2 * (size_t)m + 2))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_tcnt, 2 * FP_G_MAX * ((size_t)m / 256 + 2)))) return bail(rc);  // (round tiles of 256)
-            if ((rc = dalloc(c, &b.fp_owner, (size_t)prob->n_vars + 1, 0xFF))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_cov, (size_t)prob->n_vars + 16))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_own0, (size_t)prob->n_vars + 1))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_vlist, (size_t)L + 1))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_heavy, 4 * ((size_t)L / 64 + 2)))) return bail(rc);  // (segments of lists > 64 claims)
-            if ((rc = dalloc(c, &b.fp_pairs, (size_t)L + 1))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_blk, 2 * nblk + 2048))) return bail(rc);  // sums, offsets, changes, earliest changes
-            if ((rc = dalloc(c, &b.fp_sf, rr_T + 1))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_bnd, rr_T + 1))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_pf, rr_T + 1))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_nseg, rr_T))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_seg, (size_t)rr_T * rr_T))) return bail(rc);
-            if ((rc = dalloc(c, &b.fp_erase, rr_T))) return bail(rc);
-            b.fp_ib = ib;
-            b.fp_tb = tb;
-            b.fp_hot = 0;  // (set with the hot-variable flags below)
-            b.fp_max = FP_MAX_DEFAULT;
-            if (const char* e = getenv("ALLL_RR_FP_MAX"))  // tests: iterations left to k_rr_mw mid-run
-                b.fp_max = (uint32_t)std::max(1, std::min(250, atoi(e)));
-            c->rr_p = std::min<uint32_t>(c->rr_p, b.fp_max);
-            c->rr_pre.assign(b.fp_max + 1, nullptr);
-            if (hipHostMalloc((void**)&c->h_fp, sizeof(RRFpCtl), 0) != hipSuccess)
-                return bail(fail(ALLL_ERR_OOM, "hipHostMalloc failed"));
-            // incremental passes on instances without hot variables
-            // (ALLL_RR_INC=0: full passes only; tests, A/B)
-            bool inc = n_hot == 0;
-            if (const char* e = getenv("ALLL_RR_INC")) inc = inc && atoi(e) != 0;
-            if (inc) {
-                if ((rc = dalloc(c, &b.fp_blocker, m + 1, 0xFF)) || (rc = dalloc(c, &b.fp_covby, (size_t)prob->n_vars + 1)) ||
-                    (rc = dalloc(c, &b.fp_sc, (size_t)prob->n_vars + 1)) || (rc = dalloc(c, &b.fp_dl, 3 * (size_t)m + 16 * std::min<size_t>(m, 1u << 16) + 64)) ||
-                    (rc = dalloc(c, &b.fp_dmark, m + 1)) || (rc = dalloc(c, &b.fp_pbits, 2 * ((size_t)m / 8 + 80))) ||
-                    (rc = dalloc(c, &b.fp_log, FP_LOG_WORDS)) ||
-                    (rc = dalloc(c, &b.fp_lst, 2 * (size_t)m * ((rr_width >= 1 && rr_width <= 4) ? 4 : 8) + 16)))
-                    return bail(rc);
-                b.fp_inc = 1;
-                b.fp_inc_after = 1;
-                // the repair's limits (tests lower them to force the fallbacks: a pass that gives
-                // up, wide rounds on small instances, barriers that time out)
-                b.fp_rep_cap = FP_REP_CAP;
-                b.fp_rw_min = FP_RW_MIN;
-                b.fp_rw_timeout = FP_RW_TIMEOUT;
-                if (const char* e = getenv("ALLL_RR_REP_CAP")) b.fp_rep_cap = (uint32_t)std::max(1, atoi(e));
-                if (const char* e = getenv("ALLL_RR_RW_MIN")) b.fp_rw_min = (uint32_t)std::max(0, atoi(e));
-                if (const char* e = getenv("ALLL_RR_RW_TIMEOUT")) b.fp_rw_timeout = strtoull(e, nullptr, 10);
-                if (const char* e = getenv("ALLL_RR_INC_AFTER")) b.fp_inc_after = (uint32_t)std::max(1, atoi(e));
-            }
-        }
+    if ((rc = upload(c, &b.rr_sets, l.rr_sets, "chunk"))) return rc;
+    if ((rc = dalloc(c, &b.rr_ctl, RR_MW_CTL_WORDS)) || (rc = dalloc(c, &b.rr_gkey, RR_MW_GH)) ||
+        (rc = dalloc(c, &b.rr_gmin, RR_MW_GH, 0xFF)) || (rc = dalloc(c, &b.rr_ptr, T)) || (rc = dalloc(c, &b.rr_end, T)))
+        return rc;
+    if (!l.fp) return ALLL_OK;
+    const size_t nblk = m / FP_B + 2;
+    if ((rc = dalloc(c, &b.fp_ctl, 1)) || (rc = dalloc(c, &b.fp_in, m + FP_B)) || (rc = dalloc(c, &b.fp_turn, m + 1)) ||
+        (rc = dalloc(c, &b.fp_v4, l.fp_slots == 4 ? m + 1 : 1)) ||
+        (rc = dalloc(c, &b.fp_sole, (size_t)m * l.fp_slots + 16)) || (rc = dalloc(c, &b.fp_list, 2 * (size_t)m + 2)) ||
+        (rc = dalloc(c, &b.fp_tcnt, 2 * FP_G_MAX * ((size_t)m / 256 + 2))) ||  // (round tiles of 256)
+        (rc = dalloc(c, &b.fp_owner, nv + 1, 0xFF)) || (rc = dalloc(c, &b.fp_cov, nv + 16)) ||
+        (rc = dalloc(c, &b.fp_own0, nv + 1)) || (rc = dalloc(c, &b.fp_vlist, (size_t)L + 1)) ||
+        (rc = dalloc(c, &b.fp_heavy, 4 * ((size_t)L / 64 + 2))) ||  // (segments of lists > 64 claims)
+        (rc = dalloc(c, &b.fp_pairs, (size_t)L + 1)) ||
+        (rc = dalloc(c, &b.fp_blk, 2 * nblk + 2048)) ||  // sums, offsets, changes, earliest changes
+        (rc = dalloc(c, &b.fp_sf, T + 1)) || (rc = dalloc(c, &b.fp_bnd, T + 1)) || (rc = dalloc(c, &b.fp_pf, T + 1)) ||
+        (rc = dalloc(c, &b.fp_nseg, T)) || (rc = dalloc(c, &b.fp_seg, (size_t)T * T)) || (rc = dalloc(c, &b.fp_erase, T)))
+        return rc;
+    c->rr_p = std::min<uint32_t>(c->rr_p, b.fp_max);
+    c->rr_pre.assign(b.fp_max + 1, nullptr);
+    if (hipHostMalloc((void**)&c->h_fp, sizeof(RRFpCtl), 0) != hipSuccess) return fail(ALLL_ERR_OOM, "hipHostMalloc failed");
+    if (!l.b.fp_inc) return ALLL_OK;
+    if ((rc = dalloc(c, &b.fp_blocker, m + 1, 0xFF)) || (rc = dalloc(c, &b.fp_covby, nv + 1)) ||
+        (rc = dalloc(c, &b.fp_sc, nv + 1)) || (rc = dalloc(c, &b.fp_dl, 3 * (size_t)m + 16 * std::min<size_t>(m, 1u << 16) + 64)) ||
+        (rc = dalloc(c, &b.fp_dmark, m + 1)) || (rc = dalloc(c, &b.fp_pbits, 2 * ((size_t)m / 8 + 80))) ||
+        (rc = dalloc(c, &b.fp_log, FP_LOG_WORDS)) || (rc = dalloc(c, &b.fp_lst, 2 * (size_t)m * l.fp_slots + 16)))
+        return rc;
+    return ALLL_OK;
+}
+
+// the streaming solve with T > 1 threads: generator plans, and the generators of
+// SATInstance.h:74-86 (T t_n_clauses = n_clauses / n_threads, the last one takes the remainder), fresh
+int alloc_streaming(alll_ctx* c, const alll_options& opt, const Layout& l) {
+    const uint32_t T = l.b.srr_T;
+    if (!T) return ALLL_OK;
+    LoopBuffers& b = c->b;
+    int rc;
+    if ((rc = dalloc(c, &b.srr_gen, T + 1)) || (rc = dalloc(c, &b.srr_plan, 1)) || (rc = dalloc(c, &b.srr_first, T)))
+        return rc;
+    if (hipHostMalloc((void**)&c->h_srr, (T + 1) * sizeof(SrrGen), 0) != hipSuccess ||
+        hipHostMalloc((void**)&c->h_plan, sizeof(SrrPlan), 0) != hipSuccess ||
+        hipHostMalloc((void**)&c->h_first, T * 8ull, 0) != hipSuccess)
+        return fail(ALLL_ERR_OOM, "hipHostMalloc failed");
+    c->srr_batch = opt.stream_batch;
+    c->sgen.resize(T);
+    const uint64_t tn = l.m / T;
+    for (uint32_t t = 0; t < T; ++t) {
+        c->sgen[t].base = (uint64_t)t * tn;
+        c->sgen[t].n = t == T - 1 ? l.m - c->sgen[t].base : tn;
     }
-    if (srr_T) {
-        if ((rc = dalloc(c, &b.srr_gen, srr_T + 1)) || (rc = dalloc(c, &b.srr_plan, 1)) ||
-            (rc = dalloc(c, &b.srr_first, srr_T)))
-            return bail(rc);
-        if (hipHostMalloc((void**)&c->h_srr, (srr_T + 1) * sizeof(SrrGen), 0) != hipSuccess ||
-            hipHostMalloc((void**)&c->h_plan, sizeof(SrrPlan), 0) != hipSuccess ||
-            hipHostMalloc((void**)&c->h_first, srr_T * 8ull, 0) != hipSuccess)
-            return bail(fail(ALLL_ERR_OOM, "hipHostMalloc failed"));
-        b.srr_T = srr_T;
-        c->srr_batch = opt.stream_batch;
-        // the generators of SATInstance.h:74-86 (T t_n_clauses = n_clauses / n_threads, the last
-        // one takes the remainder), fresh
-        c->sgen.resize(srr_T);
-        const uint64_t tn = m / srr_T;
-        for (uint32_t t = 0; t < srr_T; ++t) {
-            c->sgen[t].base = (uint64_t)t * tn;
-            c->sgen[t].n = t == srr_T - 1 ? m - c->sgen[t].base : tn;
-        }
-        c->use_graph = false;
-        c->graph_note = "streaming solve with n_threads > 1: host-planned iterations (eager launches)";
+    c->use_graph = false;
+    c->graph_note = "streaming solve with n_threads > 1: host-planned iterations (eager launches)";
+    return ALLL_OK;
+}
+
+// the loop's buffers: assignment, violated mask, staging lists, MIS lists
+int alloc_loop(alll_ctx* c, const Layout& l) {
+    LoopBuffers& b = c->b;
+    const size_t slots = (size_t)l.b.n_tiles * TILE;
+    const size_t ent_words = (l.fixed_k > 0 ? (size_t)l.fixed_k + 1 : 1);
+    int rc;
+    if ((rc = dalloc(c, &b.A, b.n_words + 4)) ||  // +4: 16-byte tail loads
+        (rc = dalloc(c, &b.vmask, (size_t)l.n_tiles_padded * TILE_WORDS)) ||
+        (rc = dalloc(c, &b.tile_cnt, l.b.n_tiles)) || (rc = dalloc(c, &b.mis_cnt, l.b.n_tiles)) ||
+        (rc = dalloc(c, &b.stage[0], slots * ent_words)) || (rc = dalloc(c, &b.stage[1], slots * ent_words)) ||
+        (rc = dalloc(c, &b.mis, slots)) || (rc = dalloc(c, &b.left, slots * ent_words)) || (rc = dalloc(c, &b.tmis, slots)))
+        return rc;
+    return ALLL_OK;
+}
+
+// reference-RNG mode (alll_refrng.hip): the round's mask, offsets and draws
+int alloc_refrng(alll_ctx* c, const alll_options& opt, const Knobs& kn, const Layout& l) {
+    if (!l.refrng) return ALLL_OK;
+    LoopBuffers& b = c->b;
+    // (no clauses: the initial fill still draws; the mask pointer marks the mode)
+    if (!l.m) return dalloc(c, &b.rrng_mask, 1);
+    const uint64_t nmw = (l.m + 63) / 64, nblk = (nmw + 1023) / 1024;
+    int rc;
+    if ((rc = dalloc(c, &b.rrng_mask, (size_t)nmw)) || (rc = dalloc(c, &b.rrng_woff, (size_t)nmw)) ||
+        (rc = dalloc(c, &b.rrng_bsum, (size_t)nblk + 1)))
+        return rc;
+    b.rrng_cap = l.n_lits / 63 + 2;  // a round draws ceil(bits / 63), bits <= every literal
+    if ((rc = dalloc(c, &b.rrng_stream, (size_t)b.rrng_cap))) return rc;
+    // the parallel draws (alll_refrng.hip): engine positions for RRNG_POS_PER_DRAW per draw,
+    // jump levels until 2^levels exceeds the most draws a round can take
+    const uint64_t nmax = std::min(std::min<uint64_t>(b.rrng_cap * RRNG_POS_PER_DRAW + 64, 0xFFFFFFF0ull), kn.rrng_nmax);
+    b.rrng_nmax = (uint32_t)nmax;
+    b.rrng_levels = 1;
+    while ((1ull << b.rrng_levels) <= b.rrng_cap) ++b.rrng_levels;
+    if ((rc = dalloc(c, &b.rrng_jump, (size_t)b.rrng_levels * (nmax + 2))) || (rc = dalloc(c, &b.rrng_val, (size_t)nmax + 2)))
+        return rc;
+    if (opt.stream_batch && (rc = dalloc(c, &b.rrng_map, (size_t)l.m))) return rc;
+    return ALLL_OK;
+}
+
+// owner keys, the round robin's claimant bucket tables, cover stamps, statistics, loop state
+int alloc_owner_state(alll_ctx* c, const alll_options& opt, const Layout& l) {
+    LoopBuffers& b = c->b;
+    int rc;
+    if ((rc = dalloc(c, &b.owner, (size_t)l.vrange, 0xFF))) return rc;
+    if (l.fp) {
+        if ((rc = upload(c, &b.fp_soff, l.fp_soff, "claimant bucket")) || (rc = upload(c, &b.fp_breg, l.fp_breg, "claimant bucket")) ||
+            (rc = dalloc(c, &b.fp_bfill, l.b.n_bkt)) || (rc = dalloc(c, &b.fp_sv, (size_t)l.b.n_bkt * l.b.bkt_width)) ||
+            (rc = dalloc(c, &b.fp_sbcnt, l.b.n_bkt)))
+            return rc;
     }
-    if ((rc = dalloc(c, &b.A, b.n_words + 4))) return bail(rc);  // +4: 16-byte tail loads
-    if ((rc = dalloc(c, &b.vmask, (size_t)c->n_tiles_padded * TILE_WORDS))) return bail(rc);
-    if ((rc = dalloc(c, &b.tile_cnt, n_tiles))) return bail(rc);
-    if ((rc = dalloc(c, &b.mis_cnt, n_tiles))) return bail(rc);
-    const size_t ent_words = (fixed_k > 0 ? (size_t)fixed_k + 1 : 1);
-    if ((rc = dalloc(c, &b.stage[0], (size_t)n_tiles * TILE * ent_words))) return bail(rc);
-    if ((rc = dalloc(c, &b.stage[1], (size_t)n_tiles * TILE * ent_words))) return bail(rc);
-    if ((rc = dalloc(c, &b.mis, (size_t)n_tiles * TILE))) return bail(rc);
-    if ((rc = dalloc(c, &b.left, (size_t)n_tiles * TILE * ent_words))) return bail(rc);
-    if ((rc = dalloc(c, &b.tmis, (size_t)n_tiles * TILE))) return bail(rc);
-    if (refrng && m) {
-        const uint64_t nmw = (m + 63) / 64, nblk = (nmw + 1023) / 1024;
-        if ((rc = dalloc(c, &b.rrng_mask, (size_t)nmw)) || (rc = dalloc(c, &b.rrng_woff, (size_t)nmw)) ||
-            (rc = dalloc(c, &b.rrng_bsum, (size_t)nblk + 1)))
-            return bail(rc);
-        b.rrng_cap = L / 63 + 2;  // a round draws ceil(bits / 63), bits <= every literal
-        if ((rc = dalloc(c, &b.rrng_stream, (size_t)b.rrng_cap))) return bail(rc);
-        // the parallel draws (alll_refrng.hip): engine positions for RRNG_POS_PER_DRAW per draw,
-        // jump levels until 2^levels exceeds the most draws a round can take
-        uint64_t nmax = std::min<uint64_t>(b.rrng_cap * RRNG_POS_PER_DRAW + 64, 0xFFFFFFF0ull);
-        // (test knob: fewer positions, so that the parallel draws run past them and the
-        // one-thread chain redoes the round)
-        if (const char* e = getenv("ALLL_RRNG_NMAX"))
-            if (*e) nmax = std::max<uint64_t>(8, std::min<uint64_t>(nmax, strtoull(e, nullptr, 10)));
-        b.rrng_nmax = (uint32_t)nmax;
-        b.rrng_levels = 1;
-        while ((1ull << b.rrng_levels) <= b.rrng_cap) ++b.rrng_levels;
-        if ((rc = dalloc(c, &b.rrng_jump, (size_t)b.rrng_levels * (nmax + 2))) ||
-            (rc = dalloc(c, &b.rrng_val, (size_t)nmax + 2)))
-            return bail(rc);
-        if (opt.stream_batch && (rc = dalloc(c, &b.rrng_map, (size_t)m))) return bail(rc);
-    } else if (refrng) {
-        // (no clauses: the initial fill still draws; the mask pointer marks the mode)
-        if ((rc = dalloc(c, &b.rrng_mask, 1))) return bail(rc);
-    }
-    // skewed instances (hot variables): owner slots and round-0 buckets by vmix (alll_internal.h)
-    b.vmix_mul = 1u;
-    b.vmix_mask = 0xFFFFFFFFu;
-    uint64_t vrange = c->n_vars;  // owner slots / bucketed variable keys
-    if (n_hot) {
-        vrange = 1024;
-        while (vrange < c->n_vars) vrange <<= 1;
-        b.vmix_mul = 0x9E3779B1u;
-        b.vmix_mask = (uint32_t)(vrange - 1);
-    }
-    if ((rc = dalloc(c, &b.owner, (size_t)vrange, 0xFF))) return bail(rc);
-    {
-        uint32_t inv = b.vmix_mul;  // Newton iteration for the inverse mod 2^32 (odd multiplier)
-        for (int it = 0; it < 5; ++it) inv *= 2u - b.vmix_mul * inv;
-        b.vmix_inv = inv;
-    }
-    if (b.fp_ctl) {
-        // round robin: claimant lists by variable buckets (k_fp_bscatter / k_fp_bbuild): bucket =
-        // vmix(v) / width, width a multiple of 64, one bucket per CU
-        // when the width fits the LDS of k_fp_bbuild
-        const uint64_t span = std::max<uint64_t>(vrange, 1);
-        uint64_t width = (span + (uint64_t)c->n_cu - 1) / (uint64_t)c->n_cu;  // (two per CU: no faster)
-        width = std::max<uint64_t>(1024, (width + 63) / 64 * 64);
-        width = std::min<uint64_t>(width, 12288);
-        uint64_t nb = (span + width - 1) / width;
-        if (nb > BKT_MAX) {
-            width = ((span + BKT_MAX - 1) / BKT_MAX + 63) / 64 * 64;
-            nb = (span + width - 1) / width;
-        }
-        if (fp_bbuild_lds_bytes((uint32_t)width) > 160u * 1024 - 1024)
-            return bail(fail(ALLL_ERR_UNSUPPORTED, "round robin: %u variables exceed the claimant buckets", c->n_vars));
-        b.bkt_width = (uint32_t)width;
-        b.bkt_magic = (uint32_t)((1ull << 32) / width);
-        b.n_bkt = (uint32_t)nb;
-        b.bkt_span = (uint32_t)span;
-        std::vector<uint32_t> soff(c->n_vars + 1, 0u), breg(nb + 1, 0u);
-        parallel_chunks(L, hnt, [&](unsigned, uint64_t j0, uint64_t j1) {
-            for (uint64_t j = j0; j < j1; ++j) __atomic_fetch_add(&soff[prob->literals[j] >> 1], 1u, __ATOMIC_RELAXED);
-        });
-        uint32_t acc = 0;
-        for (uint32_t v = 0; v < c->n_vars; ++v) {
-            const uint32_t d = soff[v];
-            soff[v] = acc;
-            acc += d;
-            breg[((uint64_t)((v * b.vmix_mul) & b.vmix_mask)) / width] += d;
-        }
-        soff[c->n_vars] = acc;
-        acc = 0;
-        for (uint64_t k = 0; k <= nb; ++k) { const uint32_t d = breg[k]; breg[k] = acc; acc += d; }
-        uint32_t *d_soff = nullptr, *d_breg = nullptr;
-        if ((rc = dalloc(c, &d_soff, soff.size())) || (rc = dalloc(c, &d_breg, breg.size())) ||
-            (rc = dalloc(c, &b.fp_bfill, nb)) ||
-            (rc = dalloc(c, &b.fp_sv, (size_t)nb * width)) || (rc = dalloc(c, &b.fp_sbcnt, nb)))
-            return bail(rc);
-        if (hipStreamSynchronize(c->stream) != hipSuccess ||
-            hipMemcpy(d_soff, soff.data(), soff.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_breg, breg.data(), breg.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(ALLL_ERR_HIP, "claimant bucket upload failed"));
-        b.fp_soff = d_soff;
-        b.fp_breg = d_breg;
-    }
-    if ((rc = dalloc(c, &b.cover, (size_t)b.n_words * 32))) return bail(rc);  // whole words, zero-padded
-    if ((rc = dalloc(c, &b.tile_stats, 2 * (size_t)n_tiles))) return bail(rc);
-    if ((rc = dalloc(c, &b.delta, b.n_words))) return bail(rc);
-    if ((rc = dalloc(c, &b.state, 1))) return bail(rc);
+    if ((rc = dalloc(c, &b.cover, (size_t)b.n_words * 32)) ||  // whole words, zero-padded
+        (rc = dalloc(c, &b.tile_stats, 2 * (size_t)l.b.n_tiles)) || (rc = dalloc(c, &b.delta, b.n_words)) ||
+        (rc = dalloc(c, &b.state, 1)))
+        return rc;
     if (opt.flags & ALLL_FLAG_KERNEL_TIMING) {
-        if ((rc = dalloc(c, &b.ktime, (size_t)TIME_SLOTS * TIME_FIELDS))) return bail(rc);
         std::vector<unsigned long long> init((size_t)TIME_SLOTS * TIME_FIELDS, 0ull);
         for (uint32_t i = 0; i < TIME_SLOTS; ++i) init[(size_t)i * TIME_FIELDS] = ~0ull;
-        if (hipStreamSynchronize(c->stream) != hipSuccess ||
-            hipMemcpy(b.ktime, init.data(), init.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(ALLL_ERR_HIP, "timing buffer upload failed"));
+        if ((rc = upload(c, &b.ktime, init, "timing buffer"))) return rc;
     }
-    {
-        int khz = 0;
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0)
-            c->wall_khz = khz;
-    }
-    // ---- bucketed LFMIS round 0 (fixed width): one bucket per CU when a bucket's minima fit
-    // in LDS (else ~300-1000 power-of-2 buckets), runs of up to 16 tiles
-    if (fixed_k > 0 && !rr_T && !(opt.flags & ALLL_FLAG_ATOMIC_CLAIMS) && n_tiles > 0 && c->n_vars > 0) {
-        uint32_t shift = BKT_SHIFT_MIN;
-        while (shift < BKT_SHIFT_MAX && (vrange >> shift) > 384) ++shift;
-        uint64_t width = (vrange + (uint64_t)c->n_cu - 1) / (uint64_t)c->n_cu;
-        width = std::max<uint64_t>(width, 1u << BKT_SHIFT_MIN);
-        if (width > (1u << BKT_SHIFT_MAX)) width = 1u << shift;
-        const uint64_t nb = (vrange + width - 1) / width;
-        // skewed pair load (a literal distribution whose hubs are not all flagged hot): the
-        // fullest bucket's workgroup would serialise the round; such instances keep the atomic
-        // claims.  Hot literals never become pairs (LDS hash + owner), and vmix spreads the
-        // remaining high-degree variables of power-law instances over the buckets.
-        bool skewed = false;
-        if (nb <= BKT_MAX) {
-            std::vector<std::vector<uint64_t>> lt(hnt, std::vector<uint64_t>(nb, 0));
-            std::vector<uint64_t> lp(hnt, 0);
-            const unsigned used = parallel_chunks(L, hnt, [&](unsigned t, uint64_t j0, uint64_t j1) {
-                for (uint64_t j = j0; j < j1; ++j) {
-                    const uint32_t v = prob->literals[j] >> 1;
-                    if (n_hot && is_hot[v]) continue;
-                    ++lt[t][((v * b.vmix_mul) & b.vmix_mask) / width];
-                    ++lp[t];
-                }
-            });
-            std::vector<uint64_t> load(nb, 0);
-            uint64_t L_pairs = 0;
-            for (unsigned t = 0; t < used; ++t) {
-                for (uint64_t k = 0; k < nb; ++k) load[k] += lt[t][k];
-                L_pairs += lp[t];
-            }
-            const uint64_t mx = *std::max_element(load.begin(), load.end());
-            skewed = mx > 4 * (L_pairs / nb + 1);
-        }
-        // Runs: the tile range of every evaluation workgroup (min(n_tiles, CUs) of them, the
-        // split of k_eval_hybrid) cut into rpw runs of at most RUN_TILES_MAX tiles, so that one
-        // GPU's evaluation workgroups scatter their own runs (k_eval_hybrid `scatter`).
-        const uint32_t nblk = std::min<uint32_t>(n_tiles, (uint32_t)c->n_cu);
-        const uint32_t wmax = (n_tiles + nblk - 1) / nblk;
-        const uint32_t rpw = (wmax + RUN_TILES_MAX - 1) / RUN_TILES_MAX;
-        c->run_t0.assign((size_t)nblk * rpw + 1, 0u);
-        uint32_t rt = 1;
-        for (uint32_t w = 0; w < nblk; ++w) {
-            const uint32_t t0 = (uint32_t)((uint64_t)n_tiles * w / nblk), t1 = (uint32_t)((uint64_t)n_tiles * (w + 1) / nblk);
-            for (uint32_t j = 0; j < rpw; ++j) {
-                const uint32_t a0 = t0 + (t1 - t0) * j / rpw, a1 = t0 + (t1 - t0) * (j + 1) / rpw;
-                c->run_t0[(size_t)w * rpw + j] = a0;
-                rt = std::max(rt, a1 - a0);
-            }
-        }
-        c->run_t0.back() = n_tiles;
-        const uint64_t area = (uint64_t)nblk * rpw * rt * TILE * fixed_k;  // pairs
-        if (nb <= BKT_MAX && !skewed && area < (1ull << 32)) {  // pair positions are 32-bit in k_bresolve
-            b.bkt_width = (uint32_t)width;
-            b.bkt_magic = (uint32_t)((1ull << 32) / width);
-            b.n_bkt = (uint32_t)nb;
-            b.run_tiles = rt;
-            b.n_runs = nblk * rpw;
-            uint32_t* d_rt0 = nullptr;
-            if ((rc = dalloc(c, &d_rt0, c->run_t0.size()))) return bail(rc);
-            if (hipStreamSynchronize(c->stream) != hipSuccess ||
-                hipMemcpy(d_rt0, c->run_t0.data(), c->run_t0.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-                return bail(fail(ALLL_ERR_HIP, "run table upload failed"));
-            b.run_t0 = d_rt0;
-            const size_t run_cap = (size_t)b.run_tiles * TILE * fixed_k;
-            if ((rc = dalloc(c, &b.pairs, (size_t)b.n_runs * run_cap))) return bail(rc);
-            if ((rc = dalloc(c, &b.runtab, (size_t)b.n_bkt * b.n_runs))) return bail(rc);
-            if ((rc = dalloc(c, &b.run_pairs, b.n_runs))) return bail(rc);
-            // below this many violated clauses the atomic round 0 is cheaper (fixed costs)
-            c->bucket_min_u = std::max<uint64_t>(65536, m / 64);
-            if (const char* e = getenv("ALLL_BUCKET_MIN_U")) c->bucket_min_u = strtoull(e, nullptr, 10);
-        }
-    }
-    // ---- clause storage allocations, then drain the zero-fills before synchronous uploads
-    ClauseView& cv = c->cv;
-    cv.m = m;
-    cv.k = (uint32_t)fixed_k;
-    cv.lit_mask = 0x7FFFFFFFu;  // (bit 31: hot-variable flag)
-    uint32_t *d_lits = nullptr, *d_t = nullptr, *d_o = nullptr;
-    const uint64_t real_chunks = (m + CHUNK - 1) / CHUNK;
-    if ((rc = dalloc(c, &d_lits, L))) return bail(rc);
-    if (fixed_k > 0) {
-        if ((rc = dalloc(c, &d_t, real_chunks * CHUNK * fixed_k))) return bail(rc);
-    } else {
-        if ((rc = dalloc(c, &d_o, m + 1))) return bail(rc);
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return bail(fail(ALLL_ERR_HIP, "memset drain failed"));
+    return ALLL_OK;
+}
 
-    // ---- clauses: AoS literals (+ offsets or a chunk-transposed copy for fixed width k)
-    // hot variables (chosen above) flagged in bit 31 of every literal copy the device uses
-    std::vector<uint32_t> flagged;
-    {
-        if (n_hot) {
-            flagged.assign(prob->literals, prob->literals + L);
-            for (auto& l : flagged)
-                if (is_hot[l >> 1]) l |= 0x80000000u;
-            cv.n_hot = n_hot;
-            if (b.fp_ctl) {
-                b.fp_hot = 1;
-                if ((rc = dalloc(c, &b.fp_hv, (size_t)prob->n_vars + 16))) return bail(rc);
-            }
-            // skewed instances need more rounds before the leftovers are few enough for
-            // the single-workgroup tail (power-law 3-SAT at 10M clauses: 10 rounds)
-            if (!opt.grid_rounds) c->grid_rounds = SKEWED_GRID_ROUNDS;
-        }
-        const uint32_t* src = flagged.empty() ? prob->literals : flagged.data();
-        if (L && hipMemcpy(d_lits, src, L * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(ALLL_ERR_HIP, "literal upload failed"));
+// bucketed LFMIS round 0: the run table and the pair areas
+int alloc_round0(alll_ctx* c, const Layout& l) {
+    if (!l.bucketed) return ALLL_OK;
+    LoopBuffers& b = c->b;
+    int rc;
+    if ((rc = upload(c, &b.run_t0, l.run_t0, "run table"))) return rc;
+    const size_t run_cap = (size_t)b.run_tiles * TILE * l.fixed_k;
+    if ((rc = dalloc(c, &b.pairs, (size_t)b.n_runs * run_cap)) || (rc = dalloc(c, &b.runtab, (size_t)b.n_bkt * b.n_runs)) ||
+        (rc = dalloc(c, &b.run_pairs, b.n_runs)))
+        return rc;
+    c->bucket_min_u = l.bucket_min_u;
+    return ALLL_OK;
+}
+
+// Clause storage: AoS literals (hot variables flagged in bit 31) + offsets, or, for fixed width
+// k, a chunk-transposed copy in the planner's locality order; ragged widths add theirs.  The
+// big host arrays are planned one at a time and freed once they are on the device.
+int upload_clauses(alll_ctx* c, const alll_problem& prob, const Knobs& kn, Layout& l) {
+    LoopBuffers& b = c->b;
+    ClauseView& cv = c->cv;
+    const uint64_t m = l.m, L = l.n_lits;
+    const int K = l.fixed_k;
+    uint32_t *d_lits = nullptr, *d_t = nullptr;
+    int rc;
+    if ((rc = dalloc(c, &d_lits, L))) return rc;
+    if (K > 0) {
+        if ((rc = dalloc(c, &d_t, (m + CHUNK - 1) / CHUNK * CHUNK * K))) return rc;
+    } else if ((rc = upload(c, &cv.offs, offsets32(prob), "offset"))) {
+        return rc;
     }
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(ALLL_ERR_HIP, "memset drain failed");
+    flag_hot(prob, l);
+    if (l.cv.n_hot && b.fp_ctl && (rc = dalloc(c, &b.fp_hv, (size_t)l.n_vars + 16))) return rc;
+    const uint32_t* src = l.flagged.empty() ? prob.literals : l.flagged.data();
+    if (L && hipMemcpy(d_lits, src, L * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(ALLL_ERR_HIP, "literal upload failed");
     cv.lits = d_lits;
-    if (fixed_k > 0) {
-        // Locality order for evaluation (results do not depend on it: the violated set is a
-        // set and the LFMIS priorities are the original clause ids).  Inside every shard the
-        // clauses are evaluated sorted by (largest, second largest) variable and each clause's
-        // literals are stored by descending variable, so the gathers of slot 0 (and mostly
-        // slot 1) of a wave hit a few cache lines.  perm[p] = original id of position p.
-        //
-        // Windows (instances with more than win_vars variables; ALLL_EVAL_WINDOWS=0/1 overrides):
-        // the hybrid evaluation's LDS holds win_vars consecutive variables; clauses are first
-        // grouped by the block of their smallest variable and each tile's LDS window starts at
-        // its block, so the smallest variable (looked up by every clause) is an LDS hit.
-        std::vector<uint32_t>& perm = c->perm;
-        perm.resize(m);
-        const uint64_t win_vars = (uint64_t)b.win_words * 32;
-        bool windows = c->n_vars > win_vars;
-        if (const char* e = getenv("ALLL_EVAL_WINDOWS")) windows = atoi(e) != 0;  // tuning, tests
-        {
-            const int K = fixed_k;
-            struct Key { uint64_t k1; uint32_t k2, id; };
-            auto key_of = [&](uint64_t cl) -> Key {
-                uint32_t a = 0, b2 = 0, lo = ~0u;
-                for (int j = 0; j < K; ++j) {
-                    const uint32_t v = prob->literals[cl * K + j] >> 1;
-                    if (v > a) { b2 = a; a = v; }
-                    else if (v > b2) b2 = v;
-                    lo = std::min(lo, v);
-                }
-                const uint64_t blk = windows ? lo / win_vars : 0;
-                return {(blk << 32) | a, b2, (uint32_t)cl};
-            };
-            const unsigned nt = host_threads();
-            auto sort_range = [&](uint64_t cb0, uint64_t ce0) {
-                std::vector<Key> kv(ce0 - cb0);
-                parallel_for(ce0 - cb0, nt, [&](uint64_t i) { kv[i] = key_of(cb0 + i); });
-                parallel_sort(kv.data(), kv.size(), [](const Key& x, const Key& y) {
-                    return x.k1 != y.k1 ? x.k1 < y.k1 : (x.k2 != y.k2 ? x.k2 < y.k2 : x.id < y.id);
-                }, nt);
-                parallel_for(kv.size(), nt, [&](uint64_t i) { perm[cb0 + i] = kv[i].id; });
-            };
-            // the own shard only: the other ranks' shards keep clause order (identity perm; their
-            // violated lists come from the all-gathered clause-order mask and the AoS literals)
-            parallel_for(m, nt, [&](uint64_t i) { perm[i] = (uint32_t)i; });
-            const uint64_t cb0 = std::min<uint64_t>(m, (uint64_t)c->own_begin * TILE);
-            const uint64_t ce0 = std::min<uint64_t>(m, (uint64_t)c->own_end * TILE);
-            if (ce0 > cb0) sort_range(cb0, ce0);
-        }
-        // Packed clause ids: when the literals leave enough bits below the hot flag, slot j of
-        // every clause also carries bits [j * id_bits, (j + 1) * id_bits) of its clause id, so
-        // the evaluation emits clause ids and perm is never read on the device
-        // (ALLL_PACKED_IDS=0 keeps positions + perm; tuning, tests).
-        {
-            const uint64_t max_lit = 2ull * std::max<uint64_t>(c->n_vars, 1) - 1;
-            // (at least 6: the evaluation takes a variable's bit index from literal bits 1..5
-            // without masking)
-            const uint32_t lit_bits = std::max<uint32_t>(6, 64 - (uint32_t)__builtin_clzll(max_lit));
-            const uint32_t spare = lit_bits < 31 ? 31 - lit_bits : 0;
-            const uint32_t idb = m > 1 ? 64 - (uint32_t)__builtin_clzll(m - 1) : 1;
-            const uint32_t per = (idb + fixed_k - 1) / fixed_k;
-            bool pack = per <= spare;
-            if (const char* e = getenv("ALLL_PACKED_IDS")) pack = pack && atoi(e) != 0;
-            if (pack) {
-                cv.id_shift = lit_bits;
-                cv.id_bits = per;
-                cv.lit_mask = (1u << lit_bits) - 1u;
-            }
-        }
-        // (the own shard's chunks only: shards are tile-aligned, so they are whole chunks)
-        const uint32_t id_mask = cv.id_bits ? (1u << cv.id_bits) - 1u : 0u;
-        const uint64_t own_p0 = std::min<uint64_t>(m, (uint64_t)c->own_begin * TILE);
-        const uint64_t own_p1 = std::min<uint64_t>(m, (uint64_t)c->own_end * TILE);
-        const uint64_t g0 = own_p0 / CHUNK, g1 = (own_p1 + CHUNK - 1) / CHUNK;
-        std::vector<uint32_t> t((g1 - g0) * CHUNK * fixed_k, 0u);
-        parallel_for(own_p1 - own_p0, host_threads(), [&](uint64_t q) {
-            const uint64_t p2 = own_p0 + q;
-            uint32_t tmp[MAX_FIXED_K];
-            const uint64_t cl = perm[p2];
-            for (int j = 0; j < fixed_k; ++j)
-                tmp[j] = flagged.empty() ? prob->literals[cl * fixed_k + j] : flagged[cl * fixed_k + j];
-            // by descending variable (the hot flag, bit 31, is not part of it: slot K-1 must
-            // hold the smallest variable, which the tile's window and bit 31 of win_base cover)
-            std::sort(tmp, tmp + fixed_k, [](uint32_t x, uint32_t y) {
-                return ((x & 0x7FFFFFFFu) >> 1) > ((y & 0x7FFFFFFFu) >> 1);
-            });
-            const uint64_t g = p2 / CHUNK - g0, r = p2 % CHUNK;
-            for (int j = 0; j < fixed_k; ++j) {
-                const uint32_t idp = cv.id_bits ? ((uint32_t)(cl >> (j * cv.id_bits)) & id_mask) << cv.id_shift : 0u;
-                t[(g * fixed_k + j) * CHUNK + r] = tmp[j] | idp;
-            }
-        });
-        if (!t.empty() && hipMemcpy(d_t + g0 * CHUNK * fixed_k, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(ALLL_ERR_HIP, "transposed literal upload failed"));
-        if (!cv.id_bits) {
-            uint32_t* d_perm = nullptr;
-            if ((rc = dalloc(c, &d_perm, m))) return bail(rc);
-            if (hipStreamSynchronize(c->stream) != hipSuccess ||
-                hipMemcpy(d_perm, perm.data(), m * 4, hipMemcpyHostToDevice) != hipSuccess)
-                return bail(fail(ALLL_ERR_HIP, "permutation upload failed"));
-            cv.perm = d_perm;
-        }
+    if (K > 0) {
+        order_fixed(prob, kn, l);
+        cv.lit_mask = l.cv.lit_mask;
+        cv.id_shift = l.cv.id_shift;
+        cv.id_bits = l.cv.id_bits;
+        cv.lits_nt = l.cv.lits_nt;
+        transpose_fixed(prob, l);
+        if (!l.lits_t.empty() && hipMemcpy(d_t + l.t_chunk0 * CHUNK * K, l.lits_t.data(), l.lits_t.size() * 4,
+                                           hipMemcpyHostToDevice) != hipSuccess)
+            return fail(ALLL_ERR_HIP, "transposed literal upload failed");
+        std::vector<uint32_t>().swap(l.lits_t);
         cv.lits_t = d_t;
-        // a literal stream larger than the 256 MB Infinity Cache is read non-temporally (it
-        // cannot stay cached between iterations and would evict the assignment words of the L2
-        // lookups); ALLL_EVAL_NT=0/1 overrides (tuning, tests)
-        cv.lits_nt = (uint64_t)real_chunks * CHUNK * fixed_k * 4 > (256ull << 20) ? 1u : 0u;
-        if (const char* e = getenv("ALLL_EVAL_NT")) cv.lits_nt = atoi(e) != 0;
-        cv.offs = nullptr;
-        if (windows && m) {  // LDS window of every tile: the block of its first clause's smallest variable
-            const uint32_t lds_words = std::min<uint32_t>(b.n_words, b.win_words);
-            std::vector<uint32_t> wb(n_tiles, 0u);
-            for (uint32_t tt = c->own_begin; tt < c->own_end; ++tt) {
-                const uint64_t p = (uint64_t)tt * TILE;
-                if (p >= m) break;
-                const uint64_t cl = perm[p];
-                uint32_t lo = ~0u;
-                for (int j = 0; j < fixed_k; ++j) lo = std::min(lo, prob->literals[cl * fixed_k + j] >> 1);
-                wb[tt] = std::min<uint64_t>((uint64_t)(lo / win_vars) * b.win_words, b.n_words - lds_words);
-            }
-            // bit 31: every clause of the tile has its smallest variable in the window (all but
-            // the tiles at block boundaries), so k_eval_hybrid reads slot K-1 from LDS only
-            parallel_for(c->own_end - c->own_begin, host_threads(), [&](uint64_t q) {
-                const uint64_t tt = c->own_begin + q;
-                bool all_in = true;
-                for (uint64_t p = tt * TILE; p < std::min<uint64_t>(m, (tt + 1) * TILE) && all_in; ++p) {
-                    const uint64_t cl = perm[p];
-                    uint32_t lo = ~0u;
-                    for (int j = 0; j < fixed_k; ++j) lo = std::min(lo, prob->literals[cl * fixed_k + j] >> 1);
-                    all_in = (uint32_t)(lo / 32) - wb[tt] < lds_words;
-                }
-                if (all_in) wb[tt] |= 0x80000000u;
-            });
-            uint32_t* d_wb = nullptr;
-            if ((rc = dalloc(c, &d_wb, n_tiles))) return bail(rc);
-            if (hipStreamSynchronize(c->stream) != hipSuccess ||
-                hipMemcpy(d_wb, wb.data(), n_tiles * 4ull, hipMemcpyHostToDevice) != hipSuccess)
-                return bail(fail(ALLL_ERR_HIP, "window upload failed"));
-            b.win_base = d_wb;
-        }
-    } else {
-        std::vector<uint32_t> o32(m + 1);
-        for (uint64_t i = 0; i <= m; ++i) o32[i] = m ? (uint32_t)prob->offsets[i] : 0u;
-        if (hipMemcpy(d_o, o32.data(), (m + 1) * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(ALLL_ERR_HIP, "offset upload failed"));
-        cv.offs = d_o;
-        // Ragged widths, T = 1, not streaming: chunk-transposed copy for k_eval_ragged (the
-        // CSR arrays above stay: the LFMIS kernels read clauses by id).  ALLL_FLAG_GENERIC_CSR
-        // keeps the clause-order CSR evaluation.
-        // (the padding literal 64 * n_words must decode to an out-of-range word through the 25
-        // word-index bits k_eval_ragged extracts, and leave bit 31 clear: n_words < 2^25;
-        // ALLL_FLAG_NO_RANGED keeps the clause-order CSR evaluation like GENERIC_CSR)
-        const bool ragged = m && !rr_T && !opt.stream_batch &&
-                            !(opt.flags & (ALLL_FLAG_GENERIC_CSR | ALLL_FLAG_NO_RANGED)) &&
-                            b.n_words < (1u << 25);
-        if (ragged && (rc = build_ragged(c, prob))) return bail(rc);
+        if (!cv.id_bits && (rc = upload(c, &cv.perm, l.perm, "permutation"))) return rc;
+        window_bases(prob, l);
+        if (!l.win_base.empty() && (rc = upload(c, &b.win_base, l.win_base, "window"))) return rc;
+    } else if (l.ragged) {
+        if ((rc = order_ragged(prob, kn, l))) return fail(rc, "%s", l.err.c_str());
+        if ((rc = upload(c, &cv.rg_off, l.rg_off, "ragged layout")) || (rc = upload(c, &cv.rg_lits, l.lits_t, "ragged layout")) ||
+            (rc = upload(c, &cv.perm, l.perm, "ragged layout")) ||
+            (!l.win_base.empty() && (rc = upload(c, &b.win_base, l.win_base, "ragged layout"))))
+            return rc;
+        std::vector<uint32_t>().swap(l.lits_t);
     }
+    c->perm = std::move(l.perm);
+    return ALLL_OK;
+}
+
+// RCCL communicator (clause-sharded mode; world 1 with a comm id: a one-rank communicator that
+// runs the multi-GPU exchange path on one GPU) and the exchange's buffers
+int open_exchange(alll_ctx* c, const alll_options& opt, const Layout& l) {
+    LoopBuffers& b = c->b;
+    const bool zero_id = l.zero_id;
+    int rc;
+    if ((c->world > 1 || !zero_id) && (c->cv.k > 0 || c->cv.rg_off)) {
+        // the exchange's clause-order mask (this rank laid out its own shard only)
+        if ((rc = dalloc(c, &b.cmask, (size_t)c->n_tiles_padded * TILE_WORDS))) return rc;
+        if ((rc = dalloc(c, &b.cflag, (size_t)c->tiles_per_rank * TILE + 64))) return rc;
+    }
+    if (c->world > 1 && (rc = dalloc(c, &b.xcount, 4))) return rc;
+    if (c->world > 1 || !zero_id) {
+        if (!zero_id) {
+            ncclUniqueId id;
+            memcpy(&id, opt.comm_id, 128);
+            ncclResult_t r = ncclCommInitRank(&c->comm, c->world, id, c->rank);
+            if (r != ncclSuccess) return fail(ALLL_ERR_RCCL, "ncclCommInitRank: %s", ncclGetErrorString(r));
+        } else {
+            c->use_graph = false;  // host-staged exchange: eager launches
+            c->graph_note = "host-staged exchange (eager launches)";
+        }
+    }
+    return ALLL_OK;
+}
+
+}  // namespace
+
+int alll_create(const alll_problem* prob, const alll_options* opt_in, alll_ctx** out) {
+    if (!prob || !out) return fail(ALLL_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    alll_options opt;
+    if (opt_in) opt = *opt_in; else alll_default_options(&opt);
+    if (opt.world < 1 || opt.rank < 0 || opt.rank >= opt.world)
+        return fail(ALLL_ERR_INVALID_ARG, "bad rank %d / world %d", opt.rank, opt.world);
+    if (opt.world > ALLL_MAX_GPU_STATS) return fail(ALLL_ERR_UNSUPPORTED, "world > %d", ALLL_MAX_GPU_STATS);
+    // ---- plan on the host: the instance is validated before a device is touched
+    const Knobs kn = read_knobs();
+    Layout lay;
+    int rc;
+    if ((rc = plan_instance(*prob, opt, kn, lay))) return fail(rc, "%s", lay.err.c_str());
+
+    alll_ctx* c = nullptr;
+    if ((rc = open_device(opt, &c))) return rc;
+    auto bail = [&](int rc) { alll_destroy(c); return rc; };
+    if ((rc = plan_buckets(*prob, opt, kn, (uint32_t)c->n_cu, lay))) return bail(fail(rc, "%s", lay.err.c_str()));
+    set_shape(c, opt, kn, lay);
+    if ((rc = alloc_round_robin(c, lay)) || (rc = alloc_streaming(c, opt, lay)) || (rc = alloc_loop(c, lay)) ||
+        (rc = alloc_refrng(c, opt, kn, lay)) || (rc = alloc_owner_state(c, opt, lay)) || (rc = alloc_round0(c, lay)) ||
+        (rc = upload_clauses(c, *prob, kn, lay)))
+        return bail(rc);
+    ClauseView& cv = c->cv;
+    LoopBuffers& b = c->b;
 
     // ---- state + initial assignment
     memset(c->h_state, 0, sizeof(DevState));
     c->h_state->limit_eval = ~0ull;
     c->h_state->limit_nores = ~0ull;
     c->h_state->round_next = 1;
-    if (refrng) c->h_state->rd_state = opt.seed;  // (the random_device stand-in's state)
+    if (lay.refrng) c->h_state->rd_state = opt.seed;  // (the random_device stand-in's state)
     if (hipMemcpyAsync(b.state, c->h_state, sizeof(DevState), hipMemcpyHostToDevice, c->stream) != hipSuccess)
         return bail(fail(ALLL_ERR_HIP, "state upload failed"));
     if (launch_init_assignment(b, c->stream) != hipSuccess)
@@ -1638,33 +1075,11 @@ int alll_create(const alll_problem* prob, const alll_options* opt_in, alll_ctx**
         if (e == hipSuccess && per_cu > 0 && (uint64_t)per_cu * (uint64_t)c->n_cu < gw) b.fp_rw_min = ~0u;
         if (e != hipSuccess) (void)hipGetLastError();
         c->rw_occupancy = e == hipSuccess ? per_cu : -1;
-        if (getenv("ALLL_DEBUG_OCCUPANCY"))  // (diagnostics)
+        if (kn.debug_occupancy)  // (diagnostics)
             fprintf(stderr, "alll: k_fp_repair occupancy query %s, %d per CU, %d CUs, wide rounds %s\n",
                     hipGetErrorString(e), per_cu, c->n_cu, b.fp_rw_min == ~0u ? "off" : "on");
     }
-
-    // ---- RCCL communicator (clause-sharded mode; world 1 with a comm id: a one-rank
-    // communicator that runs the multi-GPU exchange path on one GPU)
-    bool zero_id = true;
-    for (int i = 0; i < 128; ++i) zero_id &= opt.comm_id[i] == 0;
-    if ((c->world > 1 || !zero_id) && (cv.k > 0 || cv.rg_off)) {
-        // the exchange's clause-order mask (this rank laid out its own shard only)
-        if ((rc = dalloc(c, &b.cmask, (size_t)c->n_tiles_padded * TILE_WORDS))) return bail(rc);
-        if ((rc = dalloc(c, &b.cflag, (size_t)c->tiles_per_rank * TILE + 64))) return bail(rc);
-    }
-    if (c->world > 1 && (rc = dalloc(c, &b.xcount, 4))) return bail(rc);
-    if (c->world > 1 || !zero_id) {
-        const bool zero = zero_id;
-        if (!zero) {
-            ncclUniqueId id;
-            memcpy(&id, opt.comm_id, 128);
-            ncclResult_t r = ncclCommInitRank(&c->comm, c->world, id, c->rank);
-            if (r != ncclSuccess) return bail(fail(ALLL_ERR_RCCL, "ncclCommInitRank: %s", ncclGetErrorString(r)));
-        } else {
-            c->use_graph = false;  // host-staged exchange: eager launches
-            c->graph_note = "host-staged exchange (eager launches)";
-        }
-    }
+    if ((rc = open_exchange(c, opt, lay))) return bail(rc);
     if (hipStreamSynchronize(c->stream) != hipSuccess)
         return bail(fail(ALLL_ERR_HIP, "create: stream sync failed: %s", hipGetErrorString(hipGetLastError())));
     c->hybrid = cv.k > 0 && !(opt.flags & ALLL_FLAG_NO_RANGED);
