@@ -11,11 +11,12 @@ SRC := $(PKG)/csrc
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result \
             -Iinclude -I$(SRC) -I$(ROCM)/include $(EXTRA)
 LIB := $(PKG)/liballl.so
-OBJS := $(SRC)/alll_kernels.o $(SRC)/alll_stream.o $(SRC)/alll_refrng.o $(SRC)/alll_runtime.o $(SRC)/alll_layout.o $(SRC)/alll_host.o
+OBJS := $(SRC)/alll_kernels.o $(SRC)/alll_stream.o $(SRC)/alll_refrng.o $(SRC)/alll_runtime.o $(SRC)/alll_layout.o $(SRC)/alll_host.o \
+        $(SRC)/alll_small.o $(SRC)/alll_batch.o $(SRC)/alll_batch_runtime.o
 
 all: $(LIB)
 
-$(SRC)/alll_kernels.o: $(SRC)/alll_kernels.hip $(SRC)/alll_internal.h
+$(SRC)/alll_kernels.o: $(SRC)/alll_kernels.hip $(SRC)/alll_internal.h $(SRC)/alll_philox.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 $(SRC)/alll_stream.o: $(SRC)/alll_stream.hip $(SRC)/alll_internal.h
@@ -31,6 +32,16 @@ $(SRC)/alll_layout.o: $(SRC)/alll_layout.cpp $(SRC)/alll_layout.h $(SRC)/alll_in
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 $(SRC)/alll_host.o: $(SRC)/alll_host.cpp include/alll.h
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
+# batches of LDS-resident instances: kernel, host-only planner, device set-up
+$(SRC)/alll_small.o: $(SRC)/alll_small.hip $(SRC)/alll_small.h $(SRC)/alll_batch.h $(SRC)/alll_philox.h include/alll.h
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
+$(SRC)/alll_batch.o: $(SRC)/alll_batch.cpp $(SRC)/alll_batch.h include/alll.h
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
+$(SRC)/alll_batch_runtime.o: $(SRC)/alll_batch_runtime.cpp $(SRC)/alll_small.h $(SRC)/alll_batch.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 # (linked to a temporary name and renamed: a tree snapshot taken meanwhile sees the old or the new library)

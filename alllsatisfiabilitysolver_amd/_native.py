@@ -38,6 +38,13 @@ FLAG_REFERENCE_RNG = 1 << 7
 
 MAX_GPU_STATS = 64
 
+# batches of LDS-resident instances (include/alll.h, alll_batch_*)
+BATCH_MAX_VARS = 8192
+BATCH_MAX_CLAUSES = 8192
+BATCH_MAX_LITERALS = 24576
+BATCH_MAX_SLICE = 65536
+BATCH_FIRST_SOLVED = 1 << 0
+
 # Every symbol include/alll.h declares (checked by tests/test_abi.py).
 EXPORTED = [
     "alll_version", "alll_last_error", "alll_default_options", "alll_device_count",
@@ -46,6 +53,9 @@ EXPORTED = [
     "alll_get_assignment_words", "alll_set_assignment_words", "alll_get_violated_mask",
     "alll_get_mis", "alll_bench_eval", "alll_profile", "alll_loop_times", "alll_synchronize", "alll_eval_bytes",
     "alll_layout", "alll_eval_kernel", "alll_comm_size", "alll_uses_graphs", "alll_rr_pass_log", "alll_rr_barrier_timeouts", "alll_initial_assignment", "alll_reference_initial_assignment", "alll_shard_plan", "alll_plan_multi_gpu", "alll_dimacs_parse", "alll_dimacs_read", "alll_generate_ksat",
+    "alll_batch_fits", "alll_batch_create", "alll_batch_destroy", "alll_batch_solve", "alll_batch_run",
+    "alll_batch_get_stats", "alll_batch_get_assignment_words", "alll_batch_set_assignment_words",
+    "alll_batch_set_slice",
 ]
 
 
@@ -164,6 +174,16 @@ _SIGS = {
     "alll_dimacs_read": ([ctypes.c_char_p, _u32p, _u64p, _u64p, _u32p, _u64p], ctypes.c_int),
     "alll_generate_ksat": ([ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                             ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _u32p], ctypes.c_int),
+    "alll_batch_fits": ([ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64], ctypes.c_int),
+    "alll_batch_create": ([ctypes.POINTER(Problem), _u64p, ctypes.c_uint64, ctypes.POINTER(Options),
+                           ctypes.POINTER(_vp)], ctypes.c_int),
+    "alll_batch_destroy": ([_vp], ctypes.c_int),
+    "alll_batch_solve": ([_vp, ctypes.c_uint32, ctypes.POINTER(Stats), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "alll_batch_run": ([_vp, ctypes.c_uint64, ctypes.POINTER(Stats)], ctypes.c_int),
+    "alll_batch_get_stats": ([_vp, ctypes.c_uint64, ctypes.POINTER(Stats)], ctypes.c_int),
+    "alll_batch_get_assignment_words": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_batch_set_assignment_words": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_batch_set_slice": ([_vp, ctypes.c_uint64], ctypes.c_int),
 }
 
 _lib = None

@@ -1,0 +1,285 @@
+// alll_batch_runtime.cpp -- device set-up and host loop of the batch entry points (include/alll.h,
+// alll_batch_*).  alll_batch.cpp plans and packs on the host; this file uploads the
+// image and relaunches the LDS-resident kernel (alll_small.hip) slice by slice.  The host never
+// waits inside a kernel: a launch runs at most `slice` iterations of every item.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "alll.h"
+#include "alll_batch.h"
+#include "alll_small.h"
+
+using namespace alll;
+
+extern "C" void alll_internal_set_error(const char* msg);
+
+namespace {
+
+int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    alll_internal_set_error(buf);
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                    \
+    do {                                                                                 \
+        hipError_t _e = (expr);                                                          \
+        if (_e != hipSuccess)                                                            \
+            return fail(ALLL_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
+                        __FILE__, __LINE__);                                             \
+    } while (0)
+
+// Iterations per launch.  Measured on the MI355X (profiles/batch/summary.txt):
+// items of 8192 clauses that never solve take 17.5 - 18.6 us per iteration (64 and 256 items, one
+// workgroup per CU), so a launch of 256 iterations takes 4.6 - 4.8 ms; 1024 would take 18 ms.
+constexpr uint32_t DEFAULT_SLICE = 256;
+
+// Violated sets up to this size take the kernel's one-wave serial greedy instead of the claim rounds
+// (ALLL_BATCH_SERIAL_MAX, 0 .. 64, overrides it: tuning, tests).  The results do not depend on it.
+// Measured: equal at 4, up to 3x slower at 16 and 64, so the claim rounds serve all.
+constexpr uint32_t DEFAULT_SERIAL_MAX = 0;
+
+uint32_t serial_max_knob() {
+    const char* e = getenv("ALLL_BATCH_SERIAL_MAX");
+    if (!e || !*e) return DEFAULT_SERIAL_MAX;
+    return (uint32_t)std::min<unsigned long long>(strtoull(e, nullptr, 10), 64);
+}
+
+}  // namespace
+
+struct alll_batch {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint64_t max_iters = 0;
+    uint32_t slice = DEFAULT_SLICE;
+    std::vector<SmallItem> items;
+    SmallBatch d{};
+    SmallState* h_state = nullptr;  // pinned, n_items
+    std::vector<void*> allocs;
+};
+
+namespace {
+
+template <typename T>
+int upload(alll_batch* b, const T** p, const T* src, size_t count) {
+    void* q = nullptr;
+    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+    if (hipMalloc(&q, bytes) != hipSuccess) return fail(ALLL_ERR_OOM, "hipMalloc(%zu bytes) failed", bytes);
+    b->allocs.push_back(q);
+    if (count) HIP_TRY(hipMemcpy(q, src, count * sizeof(T), hipMemcpyHostToDevice));
+    *p = static_cast<const T*>(q);
+    return ALLL_OK;
+}
+
+int read_states(alll_batch* b) {
+    HIP_TRY(hipMemcpyAsync(b->h_state, b->d.states, sizeof(SmallState) * b->d.n_items, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return ALLL_OK;
+}
+
+void to_stats(const SmallState& s, alll_stats* st) {
+    memset(st, 0, sizeof(*st));
+    st->n_iterations = s.n_iter;
+    st->n_resamples = s.n_resamples;
+    st->sum_mis_size = s.sum_mis;
+    st->avg_mis_size = s.n_iter ? s.sum_mis / s.n_iter : 0;
+    st->n_violated = s.n_violated;
+    st->solved = s.done == 1 ? 1 : 0;
+    st->n_gpus = 1;
+    st->lfmis_rounds_max = s.rounds_max;
+    st->gpu_resamples[0] = s.n_resamples;
+}
+
+uint64_t count_active(const alll_batch* b, uint64_t* n_solved) {
+    uint64_t active = 0, solved = 0;
+    for (uint32_t i = 0; i < b->d.n_items; ++i) {
+        const SmallState& s = b->h_state[i];
+        active += s.done == 0 && s.n_iter < s.limit_eval;
+        solved += s.done == 1;
+    }
+    *n_solved = solved;
+    return active;
+}
+
+// slices until no item can advance (or, first_solved, until a slice solved one more item)
+int run_slices(alll_batch* b, bool first_solved) {
+    int rc;
+    if ((rc = read_states(b))) return rc;
+    uint64_t solved0, solved;
+    uint64_t active = count_active(b, &solved0);
+    while (active) {
+        HIP_TRY(launch_small_slice(b->d, b->slice, b->stream));
+        if ((rc = read_states(b))) return rc;
+        active = count_active(b, &solved);
+        if (first_solved && solved > solved0) break;
+    }
+    return ALLL_OK;
+}
+
+void fill_all(const alll_batch* b, alll_stats* stats) {
+    if (stats)
+        for (uint32_t i = 0; i < b->d.n_items; ++i) to_stats(b->h_state[i], &stats[i]);
+}
+
+bool is_gfx950(int dev) {
+    hipDeviceProp_t p;
+    if (hipGetDeviceProperties(&p, dev) != hipSuccess) return false;
+    return strncmp(p.gcnArchName, "gfx950", 6) == 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int alll_batch_fits(uint32_t n_vars, uint64_t n_clauses, uint64_t n_literals) {
+    return batch_fits(n_vars, n_clauses, n_literals) ? 1 : 0;
+}
+
+int alll_batch_create(const alll_problem* probs, const uint64_t* seeds, uint64_t n_items, const alll_options* opt_in,
+                      alll_batch** out) {
+    if (!out) return fail(ALLL_ERR_INVALID_ARG, "batch: null argument");
+    *out = nullptr;
+    alll_options opt;
+    if (opt_in) opt = *opt_in; else alll_default_options(&opt);
+    // ---- plan on the host: the batch is validated before a device is touched
+    BatchPlan plan;
+    int rc;
+    if ((rc = plan_batch(probs, seeds, n_items, opt, plan))) return fail(rc, "%s", plan.err.c_str());
+
+    const int ndev = alll_device_count();
+    if (ndev <= 0) return fail(ALLL_ERR_NO_DEVICE, "no HIP device visible");
+    int dev = opt.device;
+    if (dev < 0) { if (hipGetDevice(&dev) != hipSuccess) dev = 0; }
+    if (dev >= ndev) return fail(ALLL_ERR_NO_DEVICE, "device %d not visible (%d devices)", dev, ndev);
+    if (!is_gfx950(dev)) return fail(ALLL_ERR_NO_DEVICE, "device %d is not gfx950 (MI355X)", dev);
+    HIP_TRY(hipSetDevice(dev));
+
+    alll_batch* b = new (std::nothrow) alll_batch();
+    if (!b) return fail(ALLL_ERR_OOM, "host allocation failed");
+    auto bail = [&](int code) { alll_batch_destroy(b); return code; };
+    b->device = dev;
+    b->max_iters = opt.max_iters;
+    b->items = std::move(plan.items);
+    b->d.n_items = (uint32_t)n_items;
+    b->d.threads = plan.threads;
+    b->d.lds = plan.lds;
+    b->d.serial_max = serial_max_knob();
+    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
+        return bail(fail(ALLL_ERR_HIP, "hipStreamCreate failed"));
+    if (hipHostMalloc((void**)&b->h_state, sizeof(SmallState) * n_items, 0) != hipSuccess)
+        return bail(fail(ALLL_ERR_OOM, "hipHostMalloc failed"));
+    memset(b->h_state, 0, sizeof(SmallState) * n_items);
+    for (uint64_t i = 0; i < n_items; ++i) b->h_state[i].limit_eval = b->h_state[i].limit_nores = ~0ull;
+    const SmallState* states = nullptr;
+    const uint32_t* A = nullptr;
+    const std::vector<uint32_t> zeros(plan.a_words, 0u);
+    if ((rc = upload(b, &b->d.items, b->items.data(), b->items.size())) ||
+        (rc = upload(b, &b->d.lits, plan.lits.data(), plan.lits.size())) ||
+        (rc = upload(b, &b->d.offs, plan.offs.data(), plan.offs.size())) ||
+        (rc = upload(b, &states, b->h_state, (size_t)n_items)) || (rc = upload(b, &A, zeros.data(), zeros.size())))
+        return bail(rc);
+    b->d.states = const_cast<SmallState*>(states);
+    b->d.A = const_cast<uint32_t*>(A);
+    hipError_t e = small_prepare();
+    if (e != hipSuccess) return bail(fail(ALLL_ERR_HIP, "kernel attributes: %s", hipGetErrorString(e)));
+    if (launch_small_init(b->d, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess)
+        return bail(fail(ALLL_ERR_HIP, "init kernel failed: %s", hipGetErrorString(hipGetLastError())));
+    *out = b;
+    return ALLL_OK;
+}
+
+int alll_batch_destroy(alll_batch* b) {
+    if (!b) return ALLL_OK;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    for (void* p : b->allocs) (void)hipFree(p);
+    if (b->h_state) (void)hipHostFree(b->h_state);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    delete b;
+    return ALLL_OK;
+}
+
+int alll_batch_solve(alll_batch* b, uint32_t flags, alll_stats* stats, int32_t* status) {
+    if (!b) return fail(ALLL_ERR_INVALID_ARG, "null batch");
+    if (flags & ~ALLL_BATCH_FIRST_SOLVED) return fail(ALLL_ERR_INVALID_ARG, "batch solve: unknown flags 0x%x", flags);
+    HIP_TRY(hipSetDevice(b->device));
+    const uint64_t cap = b->max_iters ? b->max_iters : ~0ull;
+    HIP_TRY(launch_small_limits(b->d, true, cap, b->stream));
+    if (int rc = run_slices(b, (flags & ALLL_BATCH_FIRST_SOLVED) != 0)) return rc;
+    fill_all(b, stats);
+    if (status)
+        for (uint32_t i = 0; i < b->d.n_items; ++i) status[i] = b->h_state[i].done == 1 ? ALLL_OK : ALLL_ERR_MAX_ITERS;
+    return ALLL_OK;
+}
+
+int alll_batch_run(alll_batch* b, uint64_t n_iters, alll_stats* stats) {
+    if (!b) return fail(ALLL_ERR_INVALID_ARG, "null batch");
+    HIP_TRY(hipSetDevice(b->device));
+    if (n_iters) {
+        HIP_TRY(launch_small_limits(b->d, false, n_iters, b->stream));
+        if (int rc = run_slices(b, false)) return rc;
+    } else if (stats) {
+        if (int rc = read_states(b)) return rc;
+    }
+    fill_all(b, stats);
+    return ALLL_OK;
+}
+
+int alll_batch_get_stats(alll_batch* b, uint64_t item, alll_stats* stats) {
+    if (!b || !stats) return fail(ALLL_ERR_INVALID_ARG, "null argument");
+    if (item >= b->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, b->d.n_items);
+    HIP_TRY(hipSetDevice(b->device));
+    SmallState s;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(&s, b->d.states + item, sizeof s, hipMemcpyDeviceToHost));
+    to_stats(s, stats);
+    return ALLL_OK;
+}
+
+int alll_batch_get_assignment_words(alll_batch* b, uint64_t item, uint32_t* out, uint64_t n_words) {
+    if (!b) return fail(ALLL_ERR_INVALID_ARG, "null batch");
+    if (item >= b->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, b->d.n_items);
+    const SmallItem& it = b->items[item];
+    if (!out && it.n_words) return fail(ALLL_ERR_INVALID_ARG, "null argument");
+    if (n_words < it.n_words) return fail(ALLL_ERR_INVALID_ARG, "need %u words", it.n_words);
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (it.n_words) HIP_TRY(hipMemcpy(out, b->d.A + it.a_at, it.n_words * 4ull, hipMemcpyDeviceToHost));
+    return ALLL_OK;
+}
+
+int alll_batch_set_assignment_words(alll_batch* b, uint64_t item, const uint32_t* in, uint64_t n_words) {
+    if (!b) return fail(ALLL_ERR_INVALID_ARG, "null batch");
+    if (item >= b->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, b->d.n_items);
+    const SmallItem& it = b->items[item];
+    if (!in && it.n_words) return fail(ALLL_ERR_INVALID_ARG, "null argument");
+    if (n_words < it.n_words) return fail(ALLL_ERR_INVALID_ARG, "need %u words", it.n_words);
+    HIP_TRY(hipSetDevice(b->device));
+    std::vector<uint32_t> w(in, in + it.n_words);
+    if (!w.empty() && (it.n_vars & 31)) w.back() &= (1u << (it.n_vars & 31)) - 1u;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (it.n_words) HIP_TRY(hipMemcpy(b->d.A + it.a_at, w.data(), it.n_words * 4ull, hipMemcpyHostToDevice));
+    return ALLL_OK;
+}
+
+int alll_batch_set_slice(alll_batch* b, uint64_t iters_per_launch) {
+    if (!b) return fail(ALLL_ERR_INVALID_ARG, "null batch");
+    if (iters_per_launch > ALLL_BATCH_MAX_SLICE)
+        return fail(ALLL_ERR_INVALID_ARG, "slice %llu > %u: a launch must stay bounded", (unsigned long long)iters_per_launch,
+                    ALLL_BATCH_MAX_SLICE);
+    b->slice = iters_per_launch ? (uint32_t)iters_per_launch : DEFAULT_SLICE;
+    return ALLL_OK;
+}
+
+}  // extern "C"

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "alll_internal.h"
+#include "alll_philox.h"
 
 namespace alll {
 
@@ -36,21 +37,7 @@ namespace alll {
         default: { constexpr int K = 0; CALL; } break; \
     }
 
-// ------------------------------------------------------------------------------------
-// Philox4x32-10, identical constants to oracle/alll_oracle.c (Random123 KAT-pinned).
-__device__ __forceinline__ uint32_t philox_x(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                             uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0;
-        const uint32_t n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
+// (philox_x, the Philox4x32-10 of the initial assignment and the resample: alll_philox.h)
 
 // The AoS literal copy used by the LFMIS / resample kernels carries a "hot variable" flag in
 // bit 31 (set by the host for the highest-degree variables of skewed instances).

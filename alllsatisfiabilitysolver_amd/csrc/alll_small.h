@@ -1,0 +1,33 @@
+// alll_small.h -- launchers of the LDS-resident batch kernel (alll_small.hip) for the device
+// set-up (alll_batch_runtime.cpp).  All asynchronous on `s`.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "alll_batch.h"
+
+namespace alll {
+
+// device image of a batch (what plan_batch packed, uploaded)
+struct SmallBatch {
+    const SmallItem* items;
+    SmallState* states;
+    const uint16_t* lits;
+    const uint16_t* offs;
+    uint32_t* A;
+    uint32_t n_items;
+    uint32_t threads;   // workgroup size
+    uint32_t serial_max;  // violated sets up to this size (<= 64) take the one-wave serial greedy, 0: never
+    SmallLds lds;
+};
+
+// the kernel's dynamic LDS attribute (on the batch's device, before its first slice)
+hipError_t small_prepare();
+// initial assignment of every item: word w = Philox(seed, {w, 0, 0xFFFFFFFF, 0}).x, tail cleared
+hipError_t launch_small_init(const SmallBatch& b, hipStream_t s);
+// solve = true: limit_eval = limit_nores = value (alll_solve's cap); false: limit_eval = n_iter +
+// value, limit_nores = none (alll_run); a stop at limit_nores is lifted either way
+hipError_t launch_small_limits(const SmallBatch& b, bool solve, uint64_t value, hipStream_t s);
+// one slice: every unfinished item runs at most `slice` iterations
+hipError_t launch_small_slice(const SmallBatch& b, uint32_t slice, hipStream_t s);
+
+}  // namespace alll

@@ -299,6 +299,113 @@ def device_count() -> int:
     return int(N.lib().alll_device_count())
 
 
+# ------------------------------------------------------------------------ BatchSolver
+def batch_fits(n_vars: int, n_clauses: int, n_literals: int) -> bool:
+    """True when an instance of this size can be an item of a BatchSolver (host-only)."""
+    return bool(N.lib().alll_batch_fits(n_vars, n_clauses, n_literals))
+
+
+class BatchSolver:
+    """Owns one batch of LDS-resident instances (alll_batch): item i is problems[i] =
+    (n_vars, offsets, literals) with seeds[i], solved by one workgroup; entries of `problems`
+    may repeat the same arrays (many seeds of one instance), which the device then holds once.
+    Every item computes exactly what Solver(n_vars, offsets, literals, seed=seeds[i],
+    max_iters=max_iters) computes."""
+
+    def __init__(self, problems, seeds, max_iters: int = 0, device: int = -1):
+        self._L = N.lib()
+        problems = list(problems)
+        self._seeds = np.ascontiguousarray(seeds, np.uint64)
+        if self._seeds.size != len(problems):
+            raise ValueError(f"{len(problems)} problems, {self._seeds.size} seeds")
+        self.n_items = len(problems)
+        # one converted copy per distinct pair of arrays: shared problems stay shared
+        self._keep = {}
+        arr = (N.Problem * max(1, self.n_items))()
+        self.n_vars = []
+        for i, (n_vars, offsets, literals) in enumerate(problems):
+            key = (id(offsets), id(literals))
+            if key not in self._keep:
+                self._keep[key] = (offsets, literals, np.ascontiguousarray(offsets, np.uint64),
+                                   np.ascontiguousarray(literals, np.uint32))
+            _, _, offs, lits = self._keep[key]
+            arr[i] = N.Problem(int(n_vars), 0, max(0, offs.size - 1), _p(offs, _u64p), _p(lits, _u32p))
+            self.n_vars.append(int(n_vars))
+        opt = N.Options()
+        self._L.alll_default_options(ctypes.byref(opt))
+        opt.max_iters, opt.device = max_iters, device
+        self._b = ctypes.c_void_p()
+        N.check(self._L.alll_batch_create(arr, _p(self._seeds, _u64p), self.n_items, ctypes.byref(opt),
+                                          ctypes.byref(self._b)), "alll_batch_create")
+        self._keep = None  # (the library keeps no caller pointer)
+
+    def close(self):
+        if getattr(self, "_b", None) and self._b.value:
+            self._L.alll_batch_destroy(self._b)
+            self._b = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def solve(self, first_solved: bool = False) -> List[dict]:
+        """Runs every item until it is solved or capped; one dict per item: the statistics and
+        "status" (ALLL_OK or ALLL_ERR_MAX_ITERS).  first_solved: return after the first slice
+        in which an item became solved; a later call continues."""
+        st = (N.Stats * self.n_items)()
+        status = (ctypes.c_int32 * self.n_items)()
+        N.check(self._L.alll_batch_solve(self._b, N.BATCH_FIRST_SOLVED if first_solved else 0, st, status),
+                "alll_batch_solve")
+        return [dict(st[i].as_dict(), status=int(status[i])) for i in range(self.n_items)]
+
+    def run(self, n_iters: int) -> List[dict]:
+        """n_iters more full iterations of every unfinished item (Solver.run for each)."""
+        st = (N.Stats * self.n_items)()
+        N.check(self._L.alll_batch_run(self._b, n_iters, st), "alll_batch_run")
+        return [st[i].as_dict() for i in range(self.n_items)]
+
+    def stats(self, i: int) -> dict:
+        st = N.Stats()
+        N.check(self._L.alll_batch_get_stats(self._b, i, ctypes.byref(st)), "alll_batch_get_stats")
+        return st.as_dict()
+
+    def assignment_words(self, i: int) -> np.ndarray:
+        w = np.zeros((self.n_vars[i] + 31) // 32, np.uint32)
+        N.check(self._L.alll_batch_get_assignment_words(self._b, i, _p(w, _u32p), w.size), "batch get_assignment")
+        return w
+
+    def set_assignment_words(self, i: int, w):
+        w = np.ascontiguousarray(w, np.uint32)
+        N.check(self._L.alll_batch_set_assignment_words(self._b, i, _p(w, _u32p), w.size), "batch set_assignment")
+
+    def set_slice(self, n: int):
+        """Iterations per kernel launch (0: the default)."""
+        N.check(self._L.alll_batch_set_slice(self._b, n), "alll_batch_set_slice")
+
+
+def solve_portfolio(n_vars: int, offsets, literals, seeds, max_iters: int = 0):
+    """Many seeds of one instance at once.  Returns (winning_seed, stats, assignment_words) of the
+    solved item with the fewest iterations (on a tie the lowest index), or (None, None, None)
+    when max_iters capped every seed.  The batch stops after the first slice that solved an item:
+    every item still unsolved then has run more iterations than the winner."""
+    seeds = [int(s) for s in seeds]
+    with BatchSolver([(n_vars, offsets, literals)] * len(seeds), seeds, max_iters=max_iters) as b:
+        res = b.solve(first_solved=True)
+        solved = [i for i, r in enumerate(res) if r["solved"]]
+        if not solved:
+            return None, None, None
+        best = min(solved, key=lambda i: (res[i]["n_iterations"], i))
+        return seeds[best], res[best], b.assignment_words(best)
+
+
 def shard_plan(n_clauses: int, world: int, rank: int):
     """(clause_begin, clause_end, mask_words_per_rank) of `rank` in the clause-sharded mode."""
     b, e, w = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()

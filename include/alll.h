@@ -246,6 +246,50 @@ int64_t alll_rr_barrier_timeouts(alll_ctx* ctx);
  * reference counterpart is the thread count of the -p path, example/main.cpp:76-84.) */
 int alll_comm_size(alll_ctx* ctx);
 
+/* ---- batches of LDS-resident instances -------------------------------
+ * Many small instances, or many seeds of one instance, solved at once: one workgroup owns one
+ * item and runs its whole resample loop out of LDS, a grid of workgroups the batch.  Item i
+ * behaves exactly as a context created from probs[i] with {seed = seeds[i], n_threads = 1,
+ * flags = 0, max_iters}: same initial assignment, same MIS (lexicographically first, clause
+ * order), same Philox resample, same statistics.  (No reference counterpart: the reference
+ * solves one instance per SATInstance.) */
+#define ALLL_BATCH_MAX_VARS 8192u
+#define ALLL_BATCH_MAX_CLAUSES 8192u
+#define ALLL_BATCH_MAX_LITERALS 24576u   /* a full 3-SAT item of 8192 clauses */
+#define ALLL_BATCH_MAX_SLICE 65536u      /* most iterations one kernel launch may run */
+#define ALLL_BATCH_FIRST_SOLVED (1u << 0)
+
+typedef struct alll_batch alll_batch;
+
+/* 1 when an item of this size fits a batch, else 0 (host-only). */
+int alll_batch_fits(uint32_t n_vars, uint64_t n_clauses, uint64_t n_literals);
+/* Item i = probs[i] with seed seeds[i].  Items may share offsets / literals arrays (a portfolio
+ * of seeds over one instance): arrays equal in pointer and size are stored once.  Honoured
+ * options: device, max_iters (one cap for every item); n_threads != 1, world != 1,
+ * stream_batch != 0 and any flag: ALLL_ERR_UNSUPPORTED, as is an item beyond the limits above
+ * (the message names the item).  Validated before any device is touched; keeps no caller
+ * pointer. */
+int alll_batch_create(const alll_problem* probs, const uint64_t* seeds, uint64_t n_items,
+                      const alll_options* opt, alll_batch** out);
+int alll_batch_destroy(alll_batch* b);
+/* The solve of every item: runs until each is solved or has done max_iters eval passes.  Returns
+ * ALLL_OK when the call worked; status[i] (may be NULL) is ALLL_OK or ALLL_ERR_MAX_ITERS, stats
+ * (may be NULL) holds n_items entries.  The items advance in slices of at most iters_per_launch
+ * iterations per kernel launch; with ALLL_BATCH_FIRST_SOLVED the call returns after the first
+ * slice in which an item became solved (or when no item can advance): every unfinished item has
+ * then run the same whole number of slices, and a later call continues from there.  Statistics
+ * accumulate over calls. */
+int alll_batch_solve(alll_batch* b, uint32_t flags, alll_stats* stats, int32_t* status);
+/* n_iters more full iterations (eval + MIS + resample) of every unfinished item; an item stops
+ * early only at an eval pass that finds no violated clause.  stats: n_items entries or NULL. */
+int alll_batch_run(alll_batch* b, uint64_t n_iters, alll_stats* stats);
+int alll_batch_get_stats(alll_batch* b, uint64_t item, alll_stats* stats);
+/* Bit-packed assignment of one item: ceil(n_vars/32) words. */
+int alll_batch_get_assignment_words(alll_batch* b, uint64_t item, uint32_t* out, uint64_t n_words);
+int alll_batch_set_assignment_words(alll_batch* b, uint64_t item, const uint32_t* in, uint64_t n_words);
+/* Iterations per kernel launch, 1 .. ALLL_BATCH_MAX_SLICE; 0 = the measured default. */
+int alll_batch_set_slice(alll_batch* b, uint64_t iters_per_launch);
+
 /* ---- host-side helpers (no GPU needed) ---------------------------------------------- */
 
 /* DIMACS loader with the clause semantics of example/cnf_io (cnf_header_read
