@@ -231,3 +231,59 @@ def test_lfmis_choice_is_invisible(gpu, native, oracle_mod, mixed, monkeypatch, 
         for i, (n, offs, lits) in enumerate(chains):
             st_o, A_o, _ = oracle_mod.solve(n, offs, lits, 9, max_iters=CAP, A0=np.zeros((n + 31) // 32, np.uint32))
             check_item(b, i, res[i], st_o, A_o, native, f"serial {serial}, chain {n - 1}")
+
+
+# ---------------------------------------------------------------------------------------------
+# Crafted conflict graphs (tests/lfmis_structures.py) that fit an item (at most 8192 variables,
+# 8192 clauses, 24576 literals): the chains need 2049 claim rounds and more than 64 ballot
+# groups (the prefix scan takes a second pass); the star, the copies and the dense instances put
+# thousands of claims on a few LDS addresses.
+
+@pytest.fixture(scope="module")
+def structures_batch(oracle_mod):
+    """(problems, all-false words, oracle row of the first iteration and results at max_iters = CAP)."""
+    import lfmis_structures as S
+
+    problems = [S.chain(4097), S.rchain(4097), S.star(8191, 1), S.copies(8192), S.dense(5000, 8, 3),
+                S.dense(5000, 40, 3), S.combs(16, 300, 2)]
+    from alllsatisfiabilitysolver_amd import batch_fits
+
+    for n, offs, lits in problems:
+        assert batch_fits(n, offs.size - 1, lits.size)
+    A0 = [S.all_false(n) for n, _, _ in problems]
+    want = [oracle_mod.solve(n, o, l, 9, max_iters=CAP, A0=a, trace=True) for (n, o, l), a in zip(problems, A0)]
+    # (|U|, |M|) of the first iteration: the chains, the star, the copies as constructed
+    assert [w[2][0][1:3] for w in want[:4]] == [(4097, 2049), (4097, 2049), (8191, 1), (8192, 1)]
+    assert want[6][2][0][1:3] == (4800, 2400)
+    return problems, A0, want
+
+
+@pytest.mark.parametrize("mode", ["slice1", "default", "serial64", "rounds"])
+def test_structures_batch_matches_oracle(gpu, native, structures_batch, monkeypatch, mode):
+    """One run(1) from all-false, then solve(): every item against the oracle.  mode "rounds":
+    the chains report at least their 2049 claim rounds (claim_rounds, pinned on the CPU); if a
+    later LFMIS needs fewer, the chains no longer exercise the deep rounds and must be
+    replaced."""
+    from alllsatisfiabilitysolver_amd import BatchSolver
+
+    problems, A0, want = structures_batch
+    if mode == "serial64":
+        monkeypatch.setenv("ALLL_BATCH_SERIAL_MAX", "64")
+    with BatchSolver(problems, [9] * len(problems), max_iters=CAP) as b:
+        if mode == "slice1":
+            b.set_slice(1)
+        for i, a in enumerate(A0):
+            b.set_assignment_words(i, a)
+        first = b.run(1)
+        for i, (st_o, A_o, rows) in enumerate(want):
+            it, nu, nm, dres, A_after = rows[0]
+            assert first[i]["n_violated"] == nu and first[i]["sum_mis_size"] == nm, (mode, i)
+            assert first[i]["n_resamples"] == dres, (mode, i)
+            np.testing.assert_array_equal(b.assignment_words(i), A_after, err_msg=f"{mode} item {i} step 0")
+        if mode == "rounds":
+            for i in (0, 1):
+                assert b.stats(i)["lfmis_rounds_max"] >= 2049
+            assert b.stats(6)["lfmis_rounds_max"] >= 150
+        res = b.solve()
+        for i, (st_o, A_o, _) in enumerate(want):
+            check_item(b, i, res[i], st_o, A_o, native, f"structures, {mode}")

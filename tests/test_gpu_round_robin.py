@@ -411,3 +411,74 @@ def test_rr_incremental_pass_fallbacks(gpu, oracle_mod, rr_kernel, knobs, monkey
         assert timeouts > 0 and bails
     else:
         assert wide > 0 and timeouts == 0, f"no wide repair round ran: passes {[tuple(map(int, r)) for r in inc][:12]}"
+
+
+# ---------------------------------------------------------------------------------------------
+# Crafted conflict graphs (tests/lfmis_structures.py): a deep chain needs many fixpoint passes
+# (and so the fall-back to k_rr_mw mid-iteration), a star puts one set's claims on one variable.
+# The expected values come from the oracle at the same T, never from the T = 1 table: the
+# round robin picks (513, 256) and (4097, 2048) on the chains at T = 3.
+
+RR_STRUCTURES = ["chain513", "chain4097", "combs64x300", "star20000x7", "dense8"]
+_RR_EXPECTED = {}
+
+
+def _rr_expected(o, name, T, seed, K):
+    """Oracle values of one (structure, T), computed once and shared by the four MIS modes."""
+    from lfmis_structures import all_false, structure
+
+    if (name, T) not in _RR_EXPECTED:
+        n, offs, lits = structure(name)
+        m = offs.size - 1
+        A0 = all_false(n)
+        nu, vm = o.eval_mask(offs, lits, A0)
+        M = np.sort(o.rr_mis(n, offs, lits, o.mask_to_list(m, vm), T))
+        mv = o.clause_vars(offs, lits, M)
+        steps = [o.resample_words(A0.copy(), seed, it, mv) for it in range(3)]
+        dres = int((offs[M.astype(np.int64) + 1] - offs[M.astype(np.int64)]).sum())
+        st_o, A_o, rows = o.solve(n, offs, lits, seed, max_iters=K, A0=A0, trace=True, T=T)
+        assert rows[0][1:4] == (nu, M.size, dres)
+        _RR_EXPECTED[(name, T)] = dict(nu=nu, vm=vm[: max(1, (m + 63) // 64)], M=M, dres=dres, steps=steps,
+                                       st=st_o, A=A_o, rows=rows)
+    return _RR_EXPECTED[(name, T)]
+
+
+@pytest.mark.parametrize("T", [2, 3, 16])
+@pytest.mark.parametrize("name", RR_STRUCTURES)
+def test_rr_structures_match_oracle(gpu, oracle_mod, name, T):
+    from alllsatisfiabilitysolver_amd import Solver
+    from lfmis_structures import all_false, structure
+
+    n, offs, lits = structure(name)
+    seed, K = 4242, 12
+    e = _rr_expected(oracle_mod, name, T, seed, K)
+    A0 = all_false(n)
+    # map steps: the same all-false assignment three times (iteration indices 0, 1, 2)
+    with Solver(n, offs, lits, seed=seed, n_threads=T) as s:
+        for it in range(3):
+            s.set_assignment_words(A0)
+            before = s.stats()
+            s.run(1)
+            after = s.stats()
+            np.testing.assert_array_equal(s.violated_mask(), e["vm"], err_msg=f"U, step {it}")
+            np.testing.assert_array_equal(s.mis(), e["M"], err_msg=f"M, step {it}")
+            assert after["sum_mis_size"] - before["sum_mis_size"] == e["M"].size, f"step {it}"
+            assert after["n_resamples"] - before["n_resamples"] == e["dres"], f"step {it}"
+            np.testing.assert_array_equal(s.assignment_words(), e["steps"][it], err_msg=f"A after step {it}")
+    # free run from all-false
+    with Solver(n, offs, lits, seed=seed, n_threads=T) as s:
+        s.set_assignment_words(A0)
+        for it, nu, nm, dres, A_after in e["rows"]:
+            before = s.stats()
+            s.run(1)
+            after = s.stats()
+            assert after["n_violated"] == nu, f"iter {it}"
+            assert after["sum_mis_size"] - before["sum_mis_size"] == nm, f"iter {it}"
+            assert after["n_resamples"] - before["n_resamples"] == dres, f"iter {it}"
+            np.testing.assert_array_equal(s.assignment_words(), A_after, err_msg=f"A after iter {it}")
+    with Solver(n, offs, lits, seed=seed, n_threads=T, max_iters=K) as s:
+        s.set_assignment_words(A0)
+        st = s.solve()
+        for k in ("n_iterations", "n_resamples", "avg_mis_size", "sum_mis_size", "solved"):
+            assert st[k] == e["st"][k], k
+        np.testing.assert_array_equal(s.assignment_words(), e["A"])

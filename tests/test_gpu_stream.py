@@ -190,3 +190,64 @@ def test_python_satinstance_stream_overload(gpu, oracle_mod):
     assert (st.n_iterations, st.n_resamples, st.avg_mis_size) == (
         st_o["n_iterations"], st_o["n_resamples"], st_o["avg_mis_size"])
     np.testing.assert_array_equal(oracle_mod.pack_bools(va.vars.astype(np.uint8)), A_o)
+
+
+# ---------------------------------------------------------------------------------------------
+# Crafted conflict graphs (tests/lfmis_structures.py) through the streaming solves
+
+@pytest.mark.parametrize("name", ["chain4097", "combs64x300"])
+def test_stream_structures_match_oracle(gpu, oracle_mod, name):
+    """One thread, batches of 777 clauses in the generator's order, from all-false."""
+    from alllsatisfiabilitysolver_amd import Solver
+    from lfmis_structures import all_false, structure
+
+    n, offs, lits = structure(name)
+    seed, bs, K = 31, 777, 40
+    A0 = all_false(n)
+    st_o, A_o, rows = oracle_mod.solve_stream(n, offs, lits, seed, bs, max_iters=K, A0=A0, trace=True)
+    if name == "chain4097":
+        assert st_o["solved"] == 1 and st_o["n_iterations"] == 10 and rows[0][1:3] == (4097, 1615)
+    with Solver(n, offs, lits, seed=seed, stream_batch=bs) as s:
+        s.set_assignment_words(A0)
+        for it, nu, nm, dres, A_after in rows:
+            before = s.stats()
+            s.run(1)
+            after = s.stats()
+            assert after["n_violated"] == nu, f"iter {it}"
+            assert s.mis().size == nm, f"iter {it}"
+            assert after["n_resamples"] - before["n_resamples"] == dres, f"iter {it}"
+            np.testing.assert_array_equal(s.assignment_words(), A_after, err_msg=f"A after iter {it}")
+    with Solver(n, offs, lits, seed=seed, stream_batch=bs, max_iters=K) as s:
+        s.set_assignment_words(A0)
+        st = s.solve()
+        for key in ("n_iterations", "n_resamples", "avg_mis_size", "sum_mis_size", "solved"):
+            assert st[key] == st_o[key], key
+        np.testing.assert_array_equal(s.assignment_words(), A_o)
+
+
+def test_stream_rr_chain_matches_oracle(gpu, oracle_mod):
+    """chain(513) with three generators and batches of 64, from all-false."""
+    from alllsatisfiabilitysolver_amd import Solver
+    from lfmis_structures import all_false, structure
+
+    n, offs, lits = structure("chain513")
+    seed, bs, T, K = 41, 64, 3, 400
+    A0 = all_false(n)
+    rc, st_o, A_o, rows = oracle_mod.solve_stream_rr(n, offs, lits, seed, bs, T, max_iters=K, A0=A0, trace=True)
+    assert rc in (0, 1) and rows[0][1] == 513
+    with Solver(n, offs, lits, seed=seed, stream_batch=bs, n_threads=T) as s:
+        s.set_assignment_words(A0)
+        for it, nu, nm, dres, A_after in rows[:60]:
+            before = s.stats()
+            s.run(1)
+            after = s.stats()
+            assert after["n_violated"] == nu, f"iter {it}"
+            assert after["n_resamples"] - before["n_resamples"] == dres, f"iter {it}"
+            assert s.mis().size == nm, f"iter {it}"
+            np.testing.assert_array_equal(s.assignment_words(), A_after, err_msg=f"A after iter {it}")
+    with Solver(n, offs, lits, seed=seed, stream_batch=bs, n_threads=T, max_iters=K) as s:
+        s.set_assignment_words(A0)
+        st = s.solve()
+        for key in ("n_iterations", "n_resamples", "avg_mis_size", "sum_mis_size", "solved"):
+            assert st[key] == st_o[key], key
+        np.testing.assert_array_equal(s.assignment_words(), A_o)
