@@ -5,7 +5,7 @@ MIS and Philox resampling -- runs in hand-written gfx950 HIP kernels behind the 
 include/alll.h (liballl.so).  This package is the Python front-end of that library.
 """
 from ._native import AlllError, build, lib  # noqa: F401
-from .solver import (BatchSolver, Clause, SATInstance, Solver, Statistics, VariablesArray,  # noqa: F401
+from .solver import (BatchSolver, Clause, GroupSolver, SATInstance, Solver, Statistics, VariablesArray,  # noqa: F401
                      batch_fits, solve_portfolio,
                      assignment_digest, comm_unique_id, device_count, generate_ksat, generate_mixed, gloo_exchange,
                      parse_dimacs,

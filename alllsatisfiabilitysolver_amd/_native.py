@@ -44,6 +44,8 @@ BATCH_MAX_CLAUSES = 8192
 BATCH_MAX_LITERALS = 24576
 BATCH_MAX_SLICE = 65536
 BATCH_FIRST_SOLVED = 1 << 0
+# block-diagonal groups (alll_group_*)
+GROUP_FIRST_SOLVED = 1 << 0
 
 # Every symbol include/alll.h declares (checked by tests/test_abi.py).
 EXPORTED = [
@@ -56,6 +58,9 @@ EXPORTED = [
     "alll_batch_fits", "alll_batch_create", "alll_batch_destroy", "alll_batch_solve", "alll_batch_run",
     "alll_batch_get_stats", "alll_batch_get_assignment_words", "alll_batch_set_assignment_words",
     "alll_batch_set_slice",
+    "alll_group_create", "alll_group_destroy", "alll_group_solve", "alll_group_run", "alll_group_get_stats",
+    "alll_group_get_assignment_words", "alll_group_set_assignment_words", "alll_group_layout",
+    "alll_group_eval_kernel",
 ]
 
 
@@ -184,6 +189,16 @@ _SIGS = {
     "alll_batch_get_assignment_words": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
     "alll_batch_set_assignment_words": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
     "alll_batch_set_slice": ([_vp, ctypes.c_uint64], ctypes.c_int),
+    "alll_group_create": ([ctypes.POINTER(Problem), _u64p, ctypes.c_uint64, ctypes.POINTER(Options),
+                           ctypes.POINTER(_vp)], ctypes.c_int),
+    "alll_group_destroy": ([_vp], ctypes.c_int),
+    "alll_group_solve": ([_vp, ctypes.c_uint32, ctypes.POINTER(Stats), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "alll_group_run": ([_vp, ctypes.c_uint64, ctypes.POINTER(Stats)], ctypes.c_int),
+    "alll_group_get_stats": ([_vp, ctypes.c_uint64, ctypes.POINTER(Stats)], ctypes.c_int),
+    "alll_group_get_assignment_words": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_group_set_assignment_words": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_group_layout": ([_vp], ctypes.c_int),
+    "alll_group_eval_kernel": ([_vp], ctypes.c_char_p),
 }
 
 _lib = None

@@ -1,0 +1,261 @@
+// alll_group_runtime.cpp -- device set-up and host loop of the group entry points (include/alll.h,
+// alll_group_*).  alll_group.cpp plans the block-diagonal union on the host; this
+// file creates a one-instance context from it (alll_create: the existing planner and device
+// set-up), attaches the group's tables, so that the context's captured iteration ends with the
+// per-item accounting and the keyed resample, and drives the context's own launch batches.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "alll.h"
+#include "alll_group.h"
+#include "alll_group_dev.h"
+
+using namespace alll;
+
+extern "C" void alll_internal_set_error(const char* msg);
+
+namespace {
+
+int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    alll_internal_set_error(buf);
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                    \
+    do {                                                                                 \
+        hipError_t _e = (expr);                                                          \
+        if (_e != hipSuccess)                                                            \
+            return fail(ALLL_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
+                        __FILE__, __LINE__);                                             \
+    } while (0)
+
+}  // namespace
+
+struct alll_group {
+    alll_ctx* ctx = nullptr;
+    int device = 0;
+    hipStream_t stream = nullptr;  // the context's
+    uint64_t max_iters = 0;
+    std::vector<GroupItem> items;
+    GroupDev d{};                  // (the context keeps a pointer to it)
+    GroupItemState* h_items = nullptr;  // pinned, n_items
+    std::vector<void*> allocs;
+};
+
+namespace {
+
+template <typename T>
+int upload(alll_group* g, const T** p, const T* src, size_t count) {
+    void* q = nullptr;
+    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+    if (hipMalloc(&q, bytes) != hipSuccess) return fail(ALLL_ERR_OOM, "hipMalloc(%zu bytes) failed", bytes);
+    g->allocs.push_back(q);
+    HIP_TRY(hipMemset(q, 0, bytes));
+    if (count && src) HIP_TRY(hipMemcpy(q, src, count * sizeof(T), hipMemcpyHostToDevice));
+    *p = static_cast<const T*>(q);
+    return ALLL_OK;
+}
+
+// the loop state (the context's pinned mirror) and the items' states, stream drained
+int read_all(alll_group* g) {
+    if (int rc = ctx_read_state(g->ctx)) return rc;
+    HIP_TRY(hipMemcpy(g->h_items, g->d.items, sizeof(GroupItemState) * g->d.n_items, hipMemcpyDeviceToHost));
+    return ALLL_OK;
+}
+
+void to_stats(const alll_group* g, uint64_t i, alll_stats* st) {
+    const DevState& ds = *ctx_access(g->ctx).h_state;
+    const GroupItemState& s = g->h_items[i];
+    memset(st, 0, sizeof(*st));
+    // an unfinished item has made every pass of the union (the items advance in lock step)
+    st->n_iterations = s.end_iter ? s.end_iter : ds.n_iter;
+    st->n_resamples = s.n_resamples;
+    st->sum_mis_size = s.sum_mis;
+    st->avg_mis_size = st->n_iterations ? s.sum_mis / st->n_iterations : 0;
+    st->n_violated = s.n_violated;
+    st->solved = s.end_iter ? 1 : 0;
+    st->n_gpus = 1;
+    st->lfmis_rounds_max = ds.max_rounds;   // (the union's)
+    st->lfmis_tail_rounds = ds.tail_rounds;
+    st->gpu_resamples[0] = s.n_resamples;
+}
+
+void fill_all(const alll_group* g, alll_stats* stats) {
+    if (stats)
+        for (uint32_t i = 0; i < g->d.n_items; ++i) to_stats(g, i, &stats[i]);
+}
+
+bool any_solved(const alll_group* g) {
+    for (uint32_t i = 0; i < g->d.n_items; ++i)
+        if (g->h_items[i].end_iter) return true;
+    return false;
+}
+
+}  // namespace
+
+extern "C" {
+
+int alll_group_destroy(alll_group* g) {
+    if (!g) return ALLL_OK;
+    if (g->ctx) alll_destroy(g->ctx);  // (drains the stream; its graphs hold the group's pointers)
+    (void)hipSetDevice(g->device);
+    for (void* p : g->allocs) (void)hipFree(p);
+    if (g->h_items) (void)hipHostFree(g->h_items);
+    delete g;
+    return ALLL_OK;
+}
+
+int alll_group_create(const alll_problem* probs, const uint64_t* seeds, uint64_t n_items, const alll_options* opt_in,
+                      alll_group** out) {
+    if (!out) return fail(ALLL_ERR_INVALID_ARG, "group: null argument");
+    *out = nullptr;
+    alll_options opt;
+    if (opt_in) opt = *opt_in; else alll_default_options(&opt);
+    // ---- plan on the host: the group is validated before a device is touched
+    GroupPlan plan;
+    int rc;
+    if ((rc = plan_group(probs, seeds, n_items, opt, plan))) return fail(rc, "%s", plan.err.c_str());
+
+    alll_group* g = new (std::nothrow) alll_group();
+    if (!g) return fail(ALLL_ERR_OOM, "host allocation failed");
+    auto bail = [&](int code) { alll_group_destroy(g); return code; };
+    g->max_iters = opt.max_iters;
+    g->items = std::move(plan.items);
+    g->d.n_items = (uint32_t)n_items;
+
+    // ---- the union as one context (its seed is unused: every draw is keyed by an item)
+    alll_problem un{};
+    un.n_vars = plan.n_vars;
+    un.n_clauses = plan.n_clauses;
+    un.offsets = plan.offsets.data();
+    un.literals = plan.literals.data();
+    opt.set_starts = nullptr;
+    if ((rc = alll_create(&un, &opt, &g->ctx))) return bail(rc);
+    const CtxAccess a = ctx_access(g->ctx);
+    g->device = a.device;
+    g->stream = a.stream;
+    if (hipSetDevice(g->device) != hipSuccess) return bail(fail(ALLL_ERR_HIP, "hipSetDevice failed"));
+
+    // ---- the group's tables, the items' own initial assignments
+    const GroupItemState* d_items = nullptr;
+    const unsigned long long* d_scratch = nullptr;
+    const GroupCtl* d_ctl = nullptr;
+    if ((rc = upload(g, &g->d.words, plan.words.data(), plan.words.size())) ||
+        (rc = upload(g, &g->d.clause_base, plan.clause_base.data(), plan.clause_base.size())) ||
+        (a.n_perm && (rc = upload(g, &g->d.perm, a.perm, (size_t)a.n_perm))) ||
+        (rc = upload<GroupItemState>(g, &d_items, nullptr, (size_t)n_items)) ||
+        (rc = upload<unsigned long long>(g, &d_scratch, nullptr, (size_t)n_items * GROUP_SCRATCH)) ||
+        (rc = upload<GroupCtl>(g, &d_ctl, nullptr, 1)))
+        return bail(rc);
+    g->d.items = const_cast<GroupItemState*>(d_items);
+    g->d.scratch = const_cast<unsigned long long*>(d_scratch);
+    g->d.ctl = const_cast<GroupCtl*>(d_ctl);
+    if (hipHostMalloc((void**)&g->h_items, sizeof(GroupItemState) * n_items, 0) != hipSuccess)
+        return bail(fail(ALLL_ERR_OOM, "hipHostMalloc failed"));
+    memset(g->h_items, 0, sizeof(GroupItemState) * n_items);
+    if (launch_group_init(*a.b, g->d, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess)
+        return bail(fail(ALLL_ERR_HIP, "init kernel failed: %s", hipGetErrorString(hipGetLastError())));
+    ctx_attach_group(g->ctx, &g->d);
+    *out = g;
+    return ALLL_OK;
+}
+
+int alll_group_solve(alll_group* g, uint32_t flags, alll_stats* stats, int32_t* status) {
+    if (!g) return fail(ALLL_ERR_INVALID_ARG, "null group");
+    if (flags & ~ALLL_GROUP_FIRST_SOLVED) return fail(ALLL_ERR_INVALID_ARG, "group solve: unknown flags 0x%x", flags);
+    HIP_TRY(hipSetDevice(g->device));
+    const bool first = (flags & ALLL_GROUP_FIRST_SOLVED) != 0;
+    int rc;
+    if ((rc = read_all(g))) return rc;
+    const DevState* st = ctx_access(g->ctx).h_state;
+    const uint64_t cap = g->max_iters ? g->max_iters : ~0ull;
+    if (st->done != 1 && !(first && any_solved(g))) {
+        if ((rc = ctx_write_limits(g->ctx, cap, cap))) return rc;
+        uint64_t batch = 1;
+        for (;;) {  // (launch batches as alll_solve's: every one ends with a read of the device state)
+            if ((rc = ctx_launch_iterations(g->ctx, batch))) return rc;
+            if ((rc = read_all(g))) return rc;
+            if (st->done || st->n_iter >= cap || (first && any_solved(g))) break;
+            batch = std::min<uint64_t>(batch * 2, 64);
+        }
+    }
+    fill_all(g, stats);
+    if (status)
+        for (uint32_t i = 0; i < g->d.n_items; ++i) status[i] = g->h_items[i].end_iter ? ALLL_OK : ALLL_ERR_MAX_ITERS;
+    return ALLL_OK;
+}
+
+int alll_group_run(alll_group* g, uint64_t n_iters, alll_stats* stats) {
+    if (!g) return fail(ALLL_ERR_INVALID_ARG, "null group");
+    HIP_TRY(hipSetDevice(g->device));
+    int rc;
+    if (n_iters) {
+        // (the limit is set on the device, stream-ordered before the iterations, as alll_run's)
+        HIP_TRY(launch_set_limits(*ctx_access(g->ctx).b, n_iters, g->stream));
+        if ((rc = ctx_launch_iterations(g->ctx, n_iters))) return rc;
+    }
+    if (stats) {
+        if ((rc = read_all(g))) return rc;
+        fill_all(g, stats);
+    }
+    return ALLL_OK;
+}
+
+int alll_group_get_stats(alll_group* g, uint64_t item, alll_stats* stats) {
+    if (!g || !stats) return fail(ALLL_ERR_INVALID_ARG, "null argument");
+    if (item >= g->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, g->d.n_items);
+    HIP_TRY(hipSetDevice(g->device));
+    if (int rc = read_all(g)) return rc;
+    to_stats(g, item, stats);
+    return ALLL_OK;
+}
+
+int alll_group_get_assignment_words(alll_group* g, uint64_t item, uint32_t* out, uint64_t n_words) {
+    if (!g) return fail(ALLL_ERR_INVALID_ARG, "null group");
+    if (item >= g->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, g->d.n_items);
+    const GroupItem& it = g->items[item];
+    if (!out && it.n_words) return fail(ALLL_ERR_INVALID_ARG, "null argument");
+    if (n_words < it.n_words) return fail(ALLL_ERR_INVALID_ARG, "need %u words", it.n_words);
+    HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (it.n_words)
+        HIP_TRY(hipMemcpy(out, ctx_access(g->ctx).b->A + it.word_base, it.n_words * 4ull, hipMemcpyDeviceToHost));
+    return ALLL_OK;
+}
+
+int alll_group_set_assignment_words(alll_group* g, uint64_t item, const uint32_t* in, uint64_t n_words) {
+    if (!g) return fail(ALLL_ERR_INVALID_ARG, "null group");
+    if (item >= g->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, g->d.n_items);
+    const GroupItem& it = g->items[item];
+    if (!in && it.n_words) return fail(ALLL_ERR_INVALID_ARG, "null argument");
+    if (n_words < it.n_words) return fail(ALLL_ERR_INVALID_ARG, "need %u words", it.n_words);
+    HIP_TRY(hipSetDevice(g->device));
+    if (int rc = read_all(g)) return rc;
+    // a solved item is final (as a solved context, which no later call advances): the union's loop
+    // would resample it again if its new assignment violated a clause
+    if (g->h_items[item].end_iter)
+        return fail(ALLL_ERR_INVALID_ARG, "item %llu is solved: its assignment is final", (unsigned long long)item);
+    std::vector<uint32_t> w(in, in + it.n_words);
+    if (!w.empty() && (it.n_vars & 31)) w.back() &= (1u << (it.n_vars & 31)) - 1u;
+    if (it.n_words)
+        HIP_TRY(hipMemcpy(ctx_access(g->ctx).b->A + it.word_base, w.data(), it.n_words * 4ull, hipMemcpyHostToDevice));
+    ctx_assignment_changed(g->ctx);
+    return ALLL_OK;
+}
+
+int alll_group_layout(alll_group* g) { return g ? alll_layout(g->ctx) : -1; }
+
+const char* alll_group_eval_kernel(alll_group* g) { return g ? alll_eval_kernel(g->ctx) : ""; }
+
+}  // extern "C"

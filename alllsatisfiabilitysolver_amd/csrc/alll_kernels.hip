@@ -19,6 +19,7 @@
 #include <atomic>
 #include <type_traits>
 
+#include "alll_group_dev.h"
 #include "alll_internal.h"
 #include "alll_philox.h"
 
@@ -177,6 +178,16 @@ __global__ void k_init_assignment(uint32_t* A, uint32_t n_words, uint32_t n_vars
     uint32_t x = philox_x(w, 0u, 0xFFFFFFFFu, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
     if (w == n_words - 1 && (n_vars & 31u)) x &= (1u << (n_vars & 31u)) - 1u;
     A[w] = x;
+}
+
+// Groups: the same fill with every word keyed by the item that owns it, word w of
+// item i = Philox(seeds[i], {w - word_base[i], 0, 0xFFFFFFFF, 0}).x, the bits above the item's
+// n_vars cleared in its last word (GroupWord::tail_mask).
+__global__ void k_group_init(uint32_t* A, uint32_t n_words, const GroupWord* words) {
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    const uint4 g = reinterpret_cast<const uint4*>(words)[w];  // {seed lo, seed hi, local word, tail mask}
+    A[w] = philox_x(g.z, 0u, 0xFFFFFFFFu, 0u, g.x, g.y) & g.w;
 }
 
 // Raw entry of the clause at evaluation position p with lits_t slots t[0..K-1], as the
@@ -2166,6 +2177,160 @@ __global__ __launch_bounds__(256) void k_resample_vars(LoopBuffers b) {
     cm <<= 16 * (lane & 1);
     cm |= __shfl_xor(cm, 1, 64);
     if (lead && cm) b.A[w] = (a & ~cm) | (resample_word(b.seed, it, w) & cm);
+}
+
+// ------------------------------------------------------------------------------------
+// Block-diagonal groups (alll_group_dev.h): the union of the items runs the loop
+// above unchanged; two kernels at the end of the iteration give every item its own random stream
+// and its own statistics.
+//
+// k_group_account (after the LFMIS tail): the pass's violated clauses (the evaluation's bitmask)
+// and MIS clauses (the per-tile lists and the tail's) are attributed to items by clause id -- a
+// bounded binary search in the items' clause bases, skipped while a thread stays inside the item
+// of its last clause (items are contiguous in clause order and, their variable ranges being
+// disjoint and ascending, in the evaluation orders too).  A thread adds up a run of one item, a
+// wave merges its lanes' runs, and one 64-bit atomicAdd per item and wave reaches the pass's
+// counters.  No pass since the last one accounted (a replay after the loop's gate closed): no-op.
+struct GroupAcc {
+    uint32_t item, c0, c1;  // the item of the last clause and its clause range [c0, c1)
+    uint32_t n, lits;       // clauses and literals of the current run
+};
+
+__device__ __forceinline__ uint32_t group_item_of(const GroupDev& g, uint32_t c) {
+    uint32_t lo = 0, hi = g.n_items;  // clause_base[lo] <= c < clause_base[hi] (or hi = n_items)
+    for (int s = 0; s < 32 && hi - lo > 1; ++s) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (g.clause_base[mid] <= c) lo = mid;
+        else hi = mid;
+    }
+    return lo;  // (the last item whose base is <= c: the empty items before it share its base)
+}
+
+__device__ __forceinline__ void group_send(const GroupDev& g, uint32_t item, int slot_n, int slot_l, uint32_t n,
+                                           uint32_t lits) {
+    unsigned long long* sc = g.scratch + (uint64_t)item * GROUP_SCRATCH;
+    if (n) atomicAdd(&sc[slot_n], (unsigned long long)n);
+    if (slot_l >= 0 && lits) atomicAdd(&sc[slot_l], (unsigned long long)lits);
+}
+
+__device__ __forceinline__ void group_add(const GroupDev& g, GroupAcc& a, int slot_n, int slot_l, uint32_t c,
+                                          uint32_t len) {
+    if (c - a.c0 >= a.c1 - a.c0) {  // (outside [c0, c1): another item's clause ends the run)
+        if (a.item != ~0u) group_send(g, a.item, slot_n, slot_l, a.n, a.lits);
+        a.item = group_item_of(g, c);
+        a.c0 = g.clause_base[a.item];
+        a.c1 = g.clause_base[a.item + 1];
+        a.n = 0;
+        a.lits = 0;
+    }
+    a.n += 1;
+    a.lits += len;
+}
+
+// the lanes' last runs, one atomicAdd per distinct item of the wave (all 64 lanes call)
+__device__ __forceinline__ void group_merge(const GroupDev& g, const GroupAcc& a, int slot_n, int slot_l) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long pending = __ballot(a.item != ~0u);
+    for (int s = 0; s < 64 && pending; ++s) {
+        const uint32_t it = __shfl(a.item, __ffsll((long long)pending) - 1, 64);
+        const bool mine = a.item == it;
+        uint32_t n = mine ? a.n : 0u, l = mine ? a.lits : 0u;
+        for (int o = 32; o > 0; o >>= 1) { n += __shfl_down(n, o, 64); l += __shfl_down(l, o, 64); }
+        if (lane == 0) group_send(g, it, slot_n, slot_l, n, l);
+        pending &= ~__ballot(mine);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_group_account(ClauseView cv, LoopBuffers b, GroupDev g) {
+    const DevState* st = b.state;
+    if (st->n_iter == g.ctl->acc_iter) return;
+    const uint32_t active = st->active;  // the pass runs MIS + resample (not the solved or the capped pass)
+    const uint32_t tile = blockIdx.x;
+    GroupAcc acc{~0u, 0u, 0u, 0u, 0u};
+    if (tile == b.n_tiles) {  // the MIS clauses the tail decided
+        const uint32_t cnt = active ? st->tmis_cnt : 0u;
+        for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) {
+            const uint32_t c = b.tmis[i];
+            group_add(g, acc, 1, 2, c, cv.k ? cv.k : cv.offs[c + 1] - cv.offs[c]);
+        }
+        group_merge(g, acc, 1, 2);
+        return;
+    }
+    if (threadIdx.x < TILE_WORDS) {  // wave 0: a word of the tile's violated bitmask per lane
+        const uint64_t w = (uint64_t)tile * TILE_WORDS + threadIdx.x;
+        unsigned long long x = b.vmask[w];
+        for (int s = 0; s < 64 && x; ++s) {
+            const uint32_t i = (uint32_t)__ffsll((long long)x) - 1u;
+            x &= x - 1ull;
+            // (LoopBuffers::vmask: chunk ballots in evaluation order when the layout has one, else clause order)
+            const uint64_t p = g.perm ? (w >> 2) * CHUNK + 4u * i + (w & 3u) : w * 64 + i;
+            if (p < cv.m) group_add(g, acc, 0, -1, g.perm ? g.perm[p] : (uint32_t)p, 0u);
+        }
+        group_merge(g, acc, 0, -1);
+    }
+    acc = GroupAcc{~0u, 0u, 0u, 0u, 0u};
+    const uint32_t cnt = active ? b.mis_cnt[tile] : 0u;
+    const uint32_t* mis = b.mis + (uint64_t)tile * TILE;
+    for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) {
+        const uint32_t c = mis[i];
+        group_add(g, acc, 1, 2, c, cv.k ? cv.k : cv.offs[c + 1] - cv.offs[c]);
+    }
+    group_merge(g, acc, 1, 2);
+}
+
+// The items' states, by the last workgroup of k_group_resample (the kernel boundary orders it
+// after the counts): an unfinished item with no violated clause at this pass ends here -- the
+// pass is counted, also when it is the capped pass, which runs no MIS for anybody (the zero check
+// comes before the cap check) -- and any other unfinished item adds the pass's MIS to its sums.
+__device__ void group_finish(const LoopBuffers& b, const GroupDev& g) {
+    const uint64_t it = b.state->n_iter;
+    if (it == g.ctl->acc_iter) return;
+    for (uint32_t i = threadIdx.x; i < g.n_items; i += blockDim.x) {
+        unsigned long long* sc = g.scratch + (uint64_t)i * GROUP_SCRATCH;
+        const unsigned long long nv = sc[0], nm = sc[1], nl = sc[2];
+        sc[0] = 0; sc[1] = 0; sc[2] = 0;
+        GroupItemState& s = g.items[i];
+        if (s.end_iter) continue;
+        s.n_violated = nv;
+        if (nv == 0) s.end_iter = it;
+        else { s.sum_mis += nm; s.n_resamples += nl; }
+    }
+    __syncthreads();  // (every thread has compared the pass with the last one accounted)
+    if (threadIdx.x == 0) g.ctl->acc_iter = it;
+}
+
+// k_resample_vars with the draw keyed by the item that owns the word: variable v of item i takes
+// bit v % 32 of Philox(seeds[i], {v / 32, it_lo, 0, it_hi}).x, v local to the item (items start at
+// word boundaries, so v % 32 is the bit of the union's word too).  The word's key and local index
+// (GroupWord) are loaded with the stamps; the cover-stamp scheme is k_resample_vars's.
+__global__ __launch_bounds__(256) void k_group_resample(LoopBuffers b, GroupDev g) {
+    if (blockIdx.x == gridDim.x - 1) { group_finish(b, g); return; }
+    const DevState* st = b.state;
+    const int lane = threadIdx.x & 63;
+    const bool lead = (lane & 1) == 0;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // variables 16t .. 16t+15
+    const uint32_t w = (uint32_t)(t >> 1);
+    const bool live = w < b.n_words;  // (cover is padded to whole words with zeros)
+    uint32_t a = 0;
+    uint4 key = make_uint4(0u, 0u, 0u, 0u);
+    if (lead && live) {
+        a = b.A[w];
+        key = reinterpret_cast<const uint4*>(g.words)[w];
+    }
+    uint4 c = make_uint4(0u, 0u, 0u, 0u);
+    if (live) c = reinterpret_cast<const uint4*>(b.cover)[t];
+    const uint32_t active = st->active, stamp = st->stamp;
+    const uint64_t it = st->n_iter - 1;
+    spec_fence();
+    if (!active) return;
+    const uint32_t cs[4] = {c.x, c.y, c.z, c.w};
+    uint32_t cm = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) cm |= (uint32_t)(((cs[i >> 2] >> (8 * (i & 3))) & 0xFFu) == stamp) << i;
+    cm <<= 16 * (lane & 1);
+    cm |= __shfl_xor(cm, 1, 64);
+    if (lead && cm)
+        b.A[w] = (a & ~cm) | (philox_x(key.z, (uint32_t)it, 0u, (uint32_t)(it >> 32), key.x, key.y) & cm);
 }
 
 // Allreduce exchange (ALLL_FLAG_EXCHANGE_ALLREDUCE): each rank resamples only the MIS clauses
@@ -5403,6 +5568,25 @@ hipError_t fp_repair_occupancy(const ClauseView& cv, const LoopBuffers& b, int* 
 hipError_t launch_apply_delta(const LoopBuffers& b, hipStream_t s) {
     if (b.n_words == 0) return hipSuccess;
     k_apply_delta<<<(b.n_words + 255) / 256, 256, 0, s>>>(b);
+    return hipGetLastError();
+}
+
+// ---- groups (alll_group_dev.h)
+hipError_t launch_group_init(const LoopBuffers& b, const GroupDev& g, hipStream_t s) {
+    if (b.n_words == 0) return hipSuccess;
+    k_group_init<<<(b.n_words + 255) / 256, 256, 0, s>>>(b.A, b.n_words, g.words);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_account(const ClauseView& cv, const LoopBuffers& b, const GroupDev& g, hipStream_t s) {
+    k_group_account<<<b.n_tiles + 1, 256, 0, s>>>(cv, b, g);  // a workgroup per tile and one for the tail's list
+    return hipGetLastError();
+}
+
+hipError_t launch_group_resample(const LoopBuffers& b, const GroupDev& g, hipStream_t s) {
+    const uint64_t blocks = ((uint64_t)b.n_words * 2 + 255) / 256;  // a thread per 16 variables
+    if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
+    k_group_resample<<<(uint32_t)blocks + 1, 256, 0, s>>>(b, g);  // + the workgroup of the items' states
     return hipGetLastError();
 }
 

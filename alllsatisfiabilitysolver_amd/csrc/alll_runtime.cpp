@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "alll.h"
+#include "alll_group_dev.h"
 #include "alll_internal.h"
 #include "alll_layout.h"
 
@@ -136,6 +137,9 @@ struct alll_ctx {
     unsigned long long* h_first = nullptr;
     size_t srr_cap_blk = 0, srr_cap_ent = 0, srr_cap_step = 0;
     int rw_occupancy = 0;       // resident k_fp_repair workgroups per CU found at create (-1: query failed)
+    // block-diagonal group (alll_group_runtime.cpp): the iteration ends with the
+    // group's per-item accounting and keyed resample instead of k_resample_vars; nullptr otherwise
+    const GroupDev* grp = nullptr;
 };
 
 namespace {
@@ -319,6 +323,9 @@ int enqueue_iteration(alll_ctx* c, hipEvent_t* marks, int variant) {
             if (rc) return rc;
         }
         HIP_TRY(launch_apply_delta(c->b, s));
+    } else if (c->grp) {
+        HIP_TRY(launch_group_account(c->cv, c->b, *c->grp, s));
+        HIP_TRY(launch_group_resample(c->b, *c->grp, s));
     } else {
         HIP_TRY(launch_resample(c->cv, c->b, c->own_begin, c->own_end, false, s));
     }
@@ -699,6 +706,23 @@ bool is_gfx950(int dev) {
 }
 
 }  // namespace
+
+// ---- the context as the group's runtime drives it (alll_group_dev.h)
+namespace alll {
+
+CtxAccess ctx_access(alll_ctx* c) {
+    return CtxAccess{c->device, c->stream, &c->b, &c->cv, c->h_state, c->perm.data(), c->perm.size()};
+}
+void ctx_attach_group(alll_ctx* c, const GroupDev* g) { c->grp = g; }
+int ctx_read_state(alll_ctx* c) { return read_state(c); }
+int ctx_write_limits(alll_ctx* c, uint64_t limit_eval, uint64_t limit_nores) { return write_limits(c, limit_eval, limit_nores); }
+int ctx_launch_iterations(alll_ctx* c, uint64_t n) { return launch_iterations(c, n); }
+void ctx_assignment_changed(alll_ctx* c) {
+    c->hint_u = ~0ull;
+    c->async_pending = false;
+}
+
+}  // namespace alll
 
 extern "C" {
 

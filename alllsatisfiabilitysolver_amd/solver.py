@@ -391,6 +391,96 @@ class BatchSolver:
         N.check(self._L.alll_batch_set_slice(self._b, n), "alll_batch_set_slice")
 
 
+class GroupSolver:
+    """Owns one block-diagonal group (alll_group): item i is problems[i] = (n_vars, offsets,
+    literals) with seeds[i], of any size; the items are laid side by side as one instance and the
+    one-instance loop advances all of them together.  Every item computes exactly what
+    Solver(n_vars, offsets, literals, seed=seeds[i], max_iters=max_iters) computes.  flags: the
+    FLAG_* that do not change results (NO_GRAPH, GENERIC_CSR, NO_RANGED, KERNEL_TIMING,
+    ATOMIC_CLAIMS)."""
+
+    def __init__(self, problems, seeds, max_iters: int = 0, device: int = -1, flags: int = 0):
+        self._L = N.lib()
+        problems = list(problems)
+        self._seeds = np.ascontiguousarray(seeds, np.uint64)
+        if self._seeds.size != len(problems):
+            raise ValueError(f"{len(problems)} problems, {self._seeds.size} seeds")
+        self.n_items = len(problems)
+        keep = {}  # one converted copy per distinct pair of arrays
+        arr = (N.Problem * max(1, self.n_items))()
+        self.n_vars = []
+        for i, (n_vars, offsets, literals) in enumerate(problems):
+            key = (id(offsets), id(literals))
+            if key not in keep:
+                keep[key] = (offsets, literals, np.ascontiguousarray(offsets, np.uint64),
+                             np.ascontiguousarray(literals, np.uint32))
+            _, _, offs, lits = keep[key]
+            arr[i] = N.Problem(int(n_vars), 0, max(0, offs.size - 1), _p(offs, _u64p), _p(lits, _u32p))
+            self.n_vars.append(int(n_vars))
+        opt = N.Options()
+        self._L.alll_default_options(ctypes.byref(opt))
+        opt.max_iters, opt.device, opt.flags = max_iters, device, flags
+        self._g = ctypes.c_void_p()
+        N.check(self._L.alll_group_create(arr, _p(self._seeds, _u64p), self.n_items, ctypes.byref(opt),
+                                          ctypes.byref(self._g)), "alll_group_create")
+        # (the library keeps no caller pointer)
+
+    def close(self):
+        if getattr(self, "_g", None) and self._g.value:
+            self._L.alll_group_destroy(self._g)
+            self._g = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def solve(self, first_solved: bool = False) -> List[dict]:
+        """Runs every item until it is solved or capped; one dict per item: the statistics and
+        "status" (ALLL_OK or ALLL_ERR_MAX_ITERS).  first_solved: return once at least one item
+        is solved (the winner: the solved item with the fewest iterations, the lowest index on a
+        tie); a later call continues."""
+        st = (N.Stats * self.n_items)()
+        status = (ctypes.c_int32 * self.n_items)()
+        N.check(self._L.alll_group_solve(self._g, N.GROUP_FIRST_SOLVED if first_solved else 0, st, status),
+                "alll_group_solve")
+        return [dict(st[i].as_dict(), status=int(status[i])) for i in range(self.n_items)]
+
+    def run(self, n_iters: int) -> List[dict]:
+        """n_iters more full iterations of every unfinished item (Solver.run for each)."""
+        st = (N.Stats * self.n_items)()
+        N.check(self._L.alll_group_run(self._g, n_iters, st), "alll_group_run")
+        return [st[i].as_dict() for i in range(self.n_items)]
+
+    def stats(self, i: int) -> dict:
+        st = N.Stats()
+        N.check(self._L.alll_group_get_stats(self._g, i, ctypes.byref(st)), "alll_group_get_stats")
+        return st.as_dict()
+
+    def assignment_words(self, i: int) -> np.ndarray:
+        w = np.zeros((self.n_vars[i] + 31) // 32, np.uint32)
+        N.check(self._L.alll_group_get_assignment_words(self._g, i, _p(w, _u32p), w.size), "group get_assignment")
+        return w
+
+    def set_assignment_words(self, i: int, w):
+        w = np.ascontiguousarray(w, np.uint32)
+        N.check(self._L.alll_group_set_assignment_words(self._g, i, _p(w, _u32p), w.size), "group set_assignment")
+
+    def layout(self) -> int:
+        """Layout of the union: 0 generic CSR, k > 0 fixed width k."""
+        return int(self._L.alll_group_layout(self._g))
+
+    def eval_kernel(self) -> str:
+        return self._L.alll_group_eval_kernel(self._g).decode()
+
+
 def solve_portfolio(n_vars: int, offsets, literals, seeds, max_iters: int = 0):
     """Many seeds of one instance at once.  Returns (winning_seed, stats, assignment_words) of the
     solved item with the fewest iterations (on a tie the lowest index), or (None, None, None)

@@ -290,6 +290,54 @@ int alll_batch_set_assignment_words(alll_batch* b, uint64_t item, const uint32_t
 /* Iterations per kernel launch, 1 .. ALLL_BATCH_MAX_SLICE; 0 = the measured default. */
 int alll_batch_set_slice(alll_batch* b, uint64_t iters_per_launch);
 
+/* ---- block-diagonal groups: many instances of any size at once -------
+ * The items are laid side by side as one instance with disjoint variable and clause ranges, and
+ * the one-instance loop advances all of them by one iteration per iteration: no conflict edge
+ * crosses items, so the union's violated set and its lexicographically-first MIS are the unions of
+ * the items'.  Every item draws from its own Philox stream (key seeds[i], counter word = its own
+ * word index) and keeps its own statistics and end, so item i behaves exactly as a context created
+ * from probs[i] with {seed = seeds[i], n_threads = 1, flags = 0, max_iters}: the contract of the
+ * batch above without its size limits (the union's are the loop's own).  An item
+ * ends at its first eval pass with no violated clause of its own (the pass is counted, also when it
+ * is the capped pass); its assignment and counters never change afterwards.  In alll_stats,
+ * lfmis_rounds_max and lfmis_tail_rounds are the union's (the LFMIS rounds run over all items at
+ * once), n_gpus is 1 and gpu_resamples[0] the item's n_resamples; every other field is the
+ * item's own.  (No reference counterpart: the reference solves one instance per SATInstance.) */
+#define ALLL_GROUP_FIRST_SOLVED (1u << 0)
+
+typedef struct alll_group alll_group;
+
+/* Item i = probs[i] with seed seeds[i]; items may share offsets / literals arrays (every item gets
+ * its own copy of the clauses, shifted to its variables).  Honoured options: device, max_iters (one
+ * cap for every item), grid_rounds and the flags that do not change results (ALLL_FLAG_NO_GRAPH,
+ * _GENERIC_CSR, _NO_RANGED, _KERNEL_TIMING, _ATOMIC_CLAIMS); seed is unused.  n_threads != 1,
+ * world != 1, stream_batch != 0, a non-zero comm_id, ALLL_FLAG_REFERENCE_RNG, _LFMIS,
+ * _EXCHANGE_ALLREDUCE and a union beyond the loop's limits: ALLL_ERR_UNSUPPORTED; n_items == 0 or
+ * a null pointer: ALLL_ERR_INVALID_ARG; a malformed item: the code alll_create gives, the message
+ * names the item.  Validated before any device is touched; keeps no caller pointer. */
+int alll_group_create(const alll_problem* probs, const uint64_t* seeds, uint64_t n_items,
+                      const alll_options* opt, alll_group** out);
+int alll_group_destroy(alll_group* g);
+/* Runs until every item is solved or has done max_iters eval passes.  Returns ALLL_OK when the call
+ * worked; status[i] (may be NULL) is ALLL_OK or ALLL_ERR_MAX_ITERS, stats (may be NULL) holds
+ * n_items entries.  With ALLL_GROUP_FIRST_SOLVED the call returns once at least one item is solved
+ * (at once when one already is): the solved item with the smallest n_iterations, the lowest index
+ * on a tie, is the winner whatever the others ran meanwhile; every other item has then made a whole
+ * number of iterations of its own trajectory and a later call continues from there.  Statistics
+ * accumulate over calls. */
+int alll_group_solve(alll_group* g, uint32_t flags, alll_stats* stats, int32_t* status);
+/* n_iters more full iterations (eval + MIS + resample) of every unfinished item; stops early only
+ * when all items are solved.  Asynchronous unless stats (n_items entries) != NULL. */
+int alll_group_run(alll_group* g, uint64_t n_iters, alll_stats* stats);
+int alll_group_get_stats(alll_group* g, uint64_t item, alll_stats* stats);
+/* Bit-packed assignment of one item: ceil(n_vars/32) words.  Setting the assignment of a solved
+ * item is refused (ALLL_ERR_INVALID_ARG): a solved item is final. */
+int alll_group_get_assignment_words(alll_group* g, uint64_t item, uint32_t* out, uint64_t n_words);
+int alll_group_set_assignment_words(alll_group* g, uint64_t item, const uint32_t* in, uint64_t n_words);
+/* alll_layout / alll_eval_kernel of the union. */
+int alll_group_layout(alll_group* g);
+const char* alll_group_eval_kernel(alll_group* g);
+
 /* ---- host-side helpers (no GPU needed) ---------------------------------------------- */
 
 /* DIMACS loader with the clause semantics of example/cnf_io (cnf_header_read
