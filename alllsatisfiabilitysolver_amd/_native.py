@@ -61,6 +61,8 @@ EXPORTED = [
     "alll_group_create", "alll_group_destroy", "alll_group_solve", "alll_group_run", "alll_group_get_stats",
     "alll_group_get_assignment_words", "alll_group_set_assignment_words", "alll_group_layout",
     "alll_group_eval_kernel",
+    "alll_var_threshold", "alll_biased_initial_assignment", "alll_set_var_thresholds",
+    "alll_group_set_var_thresholds",
 ]
 
 
@@ -199,6 +201,10 @@ _SIGS = {
     "alll_group_set_assignment_words": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
     "alll_group_layout": ([_vp], ctypes.c_int),
     "alll_group_eval_kernel": ([_vp], ctypes.c_char_p),
+    "alll_var_threshold": ([ctypes.c_double, _u32p], ctypes.c_int),
+    "alll_biased_initial_assignment": ([ctypes.c_uint64, ctypes.c_uint32, _u32p, _u8p], ctypes.c_int),
+    "alll_set_var_thresholds": ([_vp, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_group_set_var_thresholds": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
 }
 
 _lib = None

@@ -38,8 +38,10 @@ struct GroupDev {
 hipError_t launch_group_init(const LoopBuffers& b, const GroupDev& g, hipStream_t s);
 // after the LFMIS tail: the pass's violated clauses and MIS clauses counted per item
 hipError_t launch_group_account(const ClauseView& cv, const LoopBuffers& b, const GroupDev& g, hipStream_t s);
-// the keyed resample (in place of k_resample_vars) and, in one more workgroup, the items' states
-hipError_t launch_group_resample(const LoopBuffers& b, const GroupDev& g, hipStream_t s);
+// the keyed resample (in place of k_resample_vars) and, in one more workgroup, the items' states;
+// wbias (with b.thr): a bit per assignment word, set for the words of the items
+// that have thresholds -- k_group_resample_biased; nullptr: k_group_resample
+hipError_t launch_group_resample(const LoopBuffers& b, const GroupDev& g, const uint32_t* wbias, hipStream_t s);
 
 }  // namespace alll
 
@@ -64,5 +66,11 @@ int ctx_read_state(alll_ctx* c);  // also reports a loop that stopped on an erro
 int ctx_write_limits(alll_ctx* c, uint64_t limit_eval, uint64_t limit_nores);  // after ctx_read_state
 int ctx_launch_iterations(alll_ctx* c, uint64_t n);
 void ctx_assignment_changed(alll_ctx* c);  // the next pass's violated count is unknown
+// per-variable probabilities of a group: that the context's options allow them
+// (else ALLL_ERR_UNSUPPORTED, before any device work), then the union's thresholds and the per-word
+// bits (both null: none) for every iteration enqueued or captured from now on -- captured
+// iterations hold the old pointers by value and are dropped.  Stream drained by the caller.
+int ctx_bias_supported(alll_ctx* c);
+void ctx_set_group_bias(alll_ctx* c, const uint32_t* thr, const uint32_t* wbias);
 
 }  // namespace alll

@@ -51,6 +51,13 @@ struct alll_group {
     GroupDev d{};                  // (the context keeps a pointer to it)
     GroupItemState* h_items = nullptr;  // pinned, n_items
     std::vector<void*> allocs;
+    // per-variable probabilities, allocated at the first item that gets thresholds:
+    // the union's thresholds (zeros for unbiased items and past every item's n_vars) and a bit per
+    // assignment word of the union, set for the words of the biased items
+    const uint32_t* d_thr = nullptr;
+    const uint32_t* d_wbias = nullptr;
+    std::vector<uint32_t> wbias;   // host copy
+    std::vector<uint8_t> biased;   // per item
 };
 
 namespace {
@@ -250,6 +257,52 @@ int alll_group_set_assignment_words(alll_group* g, uint64_t item, const uint32_t
     if (!w.empty() && (it.n_vars & 31)) w.back() &= (1u << (it.n_vars & 31)) - 1u;
     if (it.n_words)
         HIP_TRY(hipMemcpy(ctx_access(g->ctx).b->A + it.word_base, w.data(), it.n_words * 4ull, hipMemcpyHostToDevice));
+    ctx_assignment_changed(g->ctx);
+    return ALLL_OK;
+}
+
+int alll_group_set_var_thresholds(alll_group* g, uint64_t item, const uint32_t* thr, uint64_t n) {
+    if (!g) return fail(ALLL_ERR_INVALID_ARG, "null group");
+    if (item >= g->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, g->d.n_items);
+    int rc;
+    if ((rc = ctx_bias_supported(g->ctx))) return rc;
+    const GroupItem& it = g->items[item];
+    if (thr && n != it.n_vars)
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: %llu entries for the %u variables of item %llu",
+                    (unsigned long long)n, it.n_vars, (unsigned long long)item);
+    HIP_TRY(hipSetDevice(g->device));
+    if ((rc = read_all(g))) return rc;  // (drains the stream)
+    const CtxAccess a = ctx_access(g->ctx);
+    if (a.h_state->n_iter != 0)
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds are set before the group's first iteration (%llu made)",
+                    (unsigned long long)a.h_state->n_iter);
+    const uint32_t n_words = a.b->n_words;  // the union's
+    const bool on = thr && it.n_words;
+    if (on && !g->d_thr) {
+        g->wbias.assign((n_words + 31) / 32, 0u);
+        g->biased.assign(g->d.n_items, 0);
+        if ((rc = upload<uint32_t>(g, &g->d_thr, nullptr, (size_t)n_words * 32)) ||
+            (rc = upload<uint32_t>(g, &g->d_wbias, nullptr, g->wbias.size())))
+            return rc;
+    }
+    if (g->d_thr) {
+        if (on)
+            HIP_TRY(hipMemcpy(const_cast<uint32_t*>(g->d_thr) + it.var_base, thr, (size_t)it.n_vars * 4,
+                              hipMemcpyHostToDevice));
+        for (uint32_t w = it.word_base; w < it.word_base + it.n_words; ++w) {
+            if (on) g->wbias[w >> 5] |= 1u << (w & 31);
+            else g->wbias[w >> 5] &= ~(1u << (w & 31));
+        }
+        g->biased[item] = on;
+        HIP_TRY(hipMemcpy(const_cast<uint32_t*>(g->d_wbias), g->wbias.data(), g->wbias.size() * 4, hipMemcpyHostToDevice));
+        const bool any = std::find(g->biased.begin(), g->biased.end(), 1) != g->biased.end();
+        ctx_set_group_bias(g->ctx, any ? g->d_thr : nullptr, any ? g->d_wbias : nullptr);
+    }
+    // the item's words again: the biased fill, or its unbiased one
+    if (launch_fill_words(a.b->A + it.word_base, it.n_words, it.n_vars, on ? g->d_thr + it.var_base : nullptr, it.seed,
+                          g->stream) != hipSuccess ||
+        hipStreamSynchronize(g->stream) != hipSuccess)
+        return fail(ALLL_ERR_HIP, "fill kernel failed: %s", hipGetErrorString(hipGetLastError()));
     ctx_assignment_changed(g->ctx);
     return ALLL_OK;
 }

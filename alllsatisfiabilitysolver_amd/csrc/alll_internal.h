@@ -372,6 +372,10 @@ struct LoopBuffers {
     uint32_t n_words;
     uint32_t n_tiles;       // tiles covering [0, m)
     uint64_t seed;
+    // per-variable resample probabilities: 32 * n_words thresholds, zeros past
+    // n_vars (a lane loads the 16 of its stamps unguarded); nullptr = the unbiased stream.  In a
+    // group: the union's, read only for the words of biased items
+    const uint32_t* thr;
 };
 
 // LDS of k_fp_bbuild for a bucket of `width` variables: counters, list starts, first claimants
@@ -379,6 +383,11 @@ inline size_t fp_bbuild_lds_bytes(uint32_t width) { return (size_t)12 * width + 
 
 // Launchers (alll_kernels.hip).  All asynchronous on `s`.
 hipError_t launch_init_assignment(const LoopBuffers& b, hipStream_t s);
+// Fill of n_words assignment words at A from one key, their variables counted from 0: the biased
+// fill from the 32 * n_words thresholds at thr, the unbiased one when thr is null.
+// A context passes its whole assignment, a group one item's words, thresholds and seed.
+hipError_t launch_fill_words(uint32_t* A, uint32_t n_words, uint32_t n_vars, const uint32_t* thr, uint64_t seed,
+                             hipStream_t s);
 hipError_t launch_init_state(const LoopBuffers& b, hipStream_t s);
 // limit_eval = n_iter + n, limit_nores = none, a stop at limit_nores is lifted (alll_run)
 hipError_t launch_set_limits(const LoopBuffers& b, uint64_t n, hipStream_t s);

@@ -13,7 +13,8 @@
 //              the violated clauses in clause order (populate_mis_parallel with one set,
 //              SATInstance.h:391-451; dependency = shared variable, :369-389).
 //   k_resample_vars  Philox4x32-10 resampling of every variable of every MIS clause
-//              (resample_clauses, SATInstance.h:340-365), one pass over the variables.
+//              (resample_clauses, SATInstance.h:340-365), one pass over the variables;
+//              k_resample_biased when the variables have their own probabilities.
 // Integer / bit work only: no MFMA.  HBM-bound on the literal stream of k_eval.
 #include <algorithm>
 #include <atomic>
@@ -188,6 +189,31 @@ __global__ void k_group_init(uint32_t* A, uint32_t n_words, const GroupWord* wor
     if (w >= n_words) return;
     const uint4 g = reinterpret_cast<const uint4*>(words)[w];  // {seed lo, seed hi, local word, tail mask}
     A[w] = philox_x(g.z, 0u, 0xFFFFFFFFu, 0u, g.x, g.y) & g.w;
+}
+
+// Per-variable probabilities: variable v draws its own 32-bit word, element v & 3
+// of the Philox call with counter word 0 = v >> 2, and is 1 when the word lies below its threshold;
+// thr = 0 pins it to 0, thr = 0xFFFFFFFF to 1 (a word of 0xFFFFFFFF is below no threshold).
+// -> bit j = the draw of the call's variable j.
+__device__ __forceinline__ uint32_t biased_bits4(const uint4 u, const uint4 t) {
+    return (uint32_t)((u.x < t.x) | (t.x == 0xFFFFFFFFu)) | (uint32_t)((u.y < t.y) | (t.y == 0xFFFFFFFFu)) << 1 |
+           (uint32_t)((u.z < t.z) | (t.z == 0xFFFFFFFFu)) << 2 | (uint32_t)((u.w < t.w) | (t.w == 0xFFFFFFFFu)) << 3;
+}
+
+// The biased fill: word w from its 32 thresholds and the 8 calls {8w + j, 0, 0xFFFFFFFE, 0} (the
+// unbiased fill's counter word 2 is 0xFFFFFFFF: disjoint draws).  thr holds 32 * n_words entries,
+// zeros past n_vars.  A group fills one item's words with it: A, thr and the variables are the item's.
+__global__ void k_init_biased(uint32_t* A, uint32_t n_words, uint32_t n_vars, const uint32_t* thr, uint64_t seed) {
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    const uint4* t4 = reinterpret_cast<const uint4*>(thr) + 8ull * w;
+    uint32_t x = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j)
+        x |= biased_bits4(philox_4(8u * w + j, 0u, 0xFFFFFFFEu, 0u, (uint32_t)seed, (uint32_t)(seed >> 32)), t4[j])
+             << (4 * j);
+    if (w == n_words - 1 && (n_vars & 31u)) x &= (1u << (n_vars & 31u)) - 1u;
+    A[w] = x;
 }
 
 // Raw entry of the clause at evaluation position p with lits_t slots t[0..K-1], as the
@@ -2179,6 +2205,48 @@ __global__ __launch_bounds__(256) void k_resample_vars(LoopBuffers b) {
     if (lead && cm) b.A[w] = (a & ~cm) | (resample_word(b.seed, it, w) & cm);
 }
 
+// The 16 biased draws of a lane: its variables are the four calls q4 .. q4 + 3
+// (counter word 0; their variables' thresholds are t4[0..3], 64 contiguous bytes), resample round
+// `it`, counter word 2 = 1 (the unbiased resample's is 0: disjoint draws).  -> bit i = variable i.
+__device__ __forceinline__ uint32_t biased_draw16(const uint4* t4, uint32_t q4, uint64_t it, uint32_t k0, uint32_t k1) {
+    uint32_t x = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j)
+        x |= biased_bits4(philox_4(q4 + j, (uint32_t)it, 1u, (uint32_t)(it >> 32), k0, k1), t4[j]) << (4 * j);
+    return x;
+}
+
+// k_resample_vars with per-variable probabilities (LoopBuffers::thr): the cover-stamp scheme is the
+// same, but a variable's draw is its own, so a lane whose 16 stamps cover anything loads its 16
+// thresholds and draws its 16 bits itself; the one exchange carries the lane's covered mask in the
+// low half and its bits in the high half.  A lane that covers nothing loads and draws nothing.
+__global__ __launch_bounds__(256) void k_resample_biased(LoopBuffers b) {
+    const DevState* st = b.state;
+    const int lane = threadIdx.x & 63;
+    const bool lead = (lane & 1) == 0;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // variables 16t .. 16t+15
+    const uint32_t w = (uint32_t)(t >> 1);
+    const bool live = w < b.n_words;  // (cover and thr are padded to whole words with zeros)
+    uint32_t a = 0;
+    if (lead && live) a = b.A[w];
+    uint4 c = make_uint4(0u, 0u, 0u, 0u);
+    if (live) c = reinterpret_cast<const uint4*>(b.cover)[t];
+    const uint32_t active = st->active, stamp = st->stamp;
+    const uint64_t it = st->n_iter - 1;
+    spec_fence();
+    if (!active) return;
+    const uint32_t cs[4] = {c.x, c.y, c.z, c.w};
+    uint32_t x = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) x |= (uint32_t)(((cs[i >> 2] >> (8 * (i & 3))) & 0xFFu) == stamp) << i;
+    if (x)
+        x |= biased_draw16(reinterpret_cast<const uint4*>(b.thr) + 4 * t, (uint32_t)(4 * t), it, (uint32_t)b.seed,
+                           (uint32_t)(b.seed >> 32)) << 16;
+    const uint32_t y = __shfl_xor(x, 1, 64);  // (the odd lane's half: variables 16 .. 31 of the word)
+    const uint32_t cm = (x & 0xFFFFu) | (y << 16);
+    if (lead && cm) b.A[w] = (a & ~cm) | (((x >> 16) | (y & 0xFFFF0000u)) & cm);
+}
+
 // ------------------------------------------------------------------------------------
 // Block-diagonal groups (alll_group_dev.h): the union of the items runs the loop
 // above unchanged; two kernels at the end of the iteration give every item its own random stream
@@ -2331,6 +2399,47 @@ __global__ __launch_bounds__(256) void k_group_resample(LoopBuffers b, GroupDev 
     cm |= __shfl_xor(cm, 1, 64);
     if (lead && cm)
         b.A[w] = (a & ~cm) | (philox_x(key.z, (uint32_t)it, 0u, (uint32_t)(it >> 32), key.x, key.y) & cm);
+}
+
+// k_group_resample for a group with biased items: bit w % 32 of wbias[w / 32] says
+// whether word w's item has thresholds (b.thr, the union's; an item's variables are local, so the
+// calls of a word's half are 8 * local word + 4 * half + 0..3).  Both lanes of a word load its key,
+// as both draw; a word of an unbiased item takes k_group_resample's draw, bit for bit.
+__global__ __launch_bounds__(256) void k_group_resample_biased(LoopBuffers b, GroupDev g, const uint32_t* wbias) {
+    if (blockIdx.x == gridDim.x - 1) { group_finish(b, g); return; }
+    const DevState* st = b.state;
+    const int lane = threadIdx.x & 63;
+    const bool lead = (lane & 1) == 0;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // variables 16t .. 16t+15
+    const uint32_t w = (uint32_t)(t >> 1);
+    const bool live = w < b.n_words;  // (cover and thr are padded to whole words with zeros)
+    uint32_t a = 0, biased = 0;
+    uint4 key = make_uint4(0u, 0u, 0u, 0u);
+    uint4 c = make_uint4(0u, 0u, 0u, 0u);
+    if (live) {
+        if (lead) a = b.A[w];
+        key = reinterpret_cast<const uint4*>(g.words)[w];
+        biased = (wbias[w >> 5] >> (w & 31u)) & 1u;
+        c = reinterpret_cast<const uint4*>(b.cover)[t];
+    }
+    const uint32_t active = st->active, stamp = st->stamp;
+    const uint64_t it = st->n_iter - 1;
+    spec_fence();
+    if (!active) return;
+    const uint32_t cs[4] = {c.x, c.y, c.z, c.w};
+    uint32_t x = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) x |= (uint32_t)(((cs[i >> 2] >> (8 * (i & 3))) & 0xFFu) == stamp) << i;
+    if (x && biased)
+        x |= biased_draw16(reinterpret_cast<const uint4*>(b.thr) + 4 * t, 8u * key.z + 4u * (uint32_t)(lane & 1), it,
+                           key.x, key.y) << 16;
+    const uint32_t y = __shfl_xor(x, 1, 64);
+    const uint32_t cm = (x & 0xFFFFu) | (y << 16);
+    if (lead && cm) {
+        const uint32_t bits = biased ? (x >> 16) | (y & 0xFFFF0000u)
+                                     : philox_x(key.z, (uint32_t)it, 0u, (uint32_t)(it >> 32), key.x, key.y);
+        b.A[w] = (a & ~cm) | (bits & cm);
+    }
 }
 
 // Allreduce exchange (ALLL_FLAG_EXCHANGE_ALLREDUCE): each rank resamples only the MIS clauses
@@ -5201,6 +5310,14 @@ hipError_t launch_init_assignment(const LoopBuffers& b, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_fill_words(uint32_t* A, uint32_t n_words, uint32_t n_vars, const uint32_t* thr, uint64_t seed,
+                             hipStream_t s) {
+    if (n_words == 0) return hipSuccess;
+    if (thr) k_init_biased<<<(n_words + 255) / 256, 256, 0, s>>>(A, n_words, n_vars, thr, seed);
+    else k_init_assignment<<<(n_words + 255) / 256, 256, 0, s>>>(A, n_words, n_vars, seed);
+    return hipGetLastError();
+}
+
 __global__ void k_set_limits(DevState* st, uint64_t n) {
     if (threadIdx.x != 0) return;
     st->limit_eval = st->n_iter + n;
@@ -5554,7 +5671,8 @@ hipError_t launch_resample(const ClauseView& cv, const LoopBuffers& b, uint32_t 
     if (b.n_vars == 0) return hipSuccess;
     const uint64_t blocks = ((uint64_t)b.n_words * 2 + 255) / 256;  // a thread per 16 variables
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    k_resample_vars<<<(uint32_t)blocks, 256, 0, s>>>(b);
+    if (b.thr) k_resample_biased<<<(uint32_t)blocks, 256, 0, s>>>(b);  // (per-variable probabilities)
+    else k_resample_vars<<<(uint32_t)blocks, 256, 0, s>>>(b);
     return hipGetLastError();
 }
 
@@ -5583,10 +5701,12 @@ hipError_t launch_group_account(const ClauseView& cv, const LoopBuffers& b, cons
     return hipGetLastError();
 }
 
-hipError_t launch_group_resample(const LoopBuffers& b, const GroupDev& g, hipStream_t s) {
+hipError_t launch_group_resample(const LoopBuffers& b, const GroupDev& g, const uint32_t* wbias, hipStream_t s) {
     const uint64_t blocks = ((uint64_t)b.n_words * 2 + 255) / 256;  // a thread per 16 variables
     if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
-    k_group_resample<<<(uint32_t)blocks + 1, 256, 0, s>>>(b, g);  // + the workgroup of the items' states
+    // + the workgroup of the items' states
+    if (wbias && b.thr) k_group_resample_biased<<<(uint32_t)blocks + 1, 256, 0, s>>>(b, g, wbias);
+    else k_group_resample<<<(uint32_t)blocks + 1, 256, 0, s>>>(b, g);
     return hipGetLastError();
 }
 

@@ -22,4 +22,20 @@ __device__ __forceinline__ uint32_t philox_x(uint32_t c0, uint32_t c1, uint32_t 
     return c0;
 }
 
+// The same ten rounds, all four output words in Random123 order (philox_x is element 0): the
+// biased draws take one word per variable, element v & 3 of counter v >> 2.
+__device__ __forceinline__ uint4 philox_4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                          uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = hi1 ^ c1 ^ k0;
+        const uint32_t n2 = hi0 ^ c3 ^ k1;
+        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
 }  // namespace alll

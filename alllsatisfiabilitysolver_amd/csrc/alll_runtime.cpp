@@ -140,6 +140,10 @@ struct alll_ctx {
     // block-diagonal group (alll_group_runtime.cpp): the iteration ends with the
     // group's per-item accounting and keyed resample instead of k_resample_vars; nullptr otherwise
     const GroupDev* grp = nullptr;
+    // per-variable probabilities: the context's own copy of the thresholds (b.thr
+    // points to it while they are set), and a group's per-word bits
+    uint32_t* d_thr = nullptr;
+    const uint32_t* grp_wbias = nullptr;
 };
 
 namespace {
@@ -325,7 +329,7 @@ int enqueue_iteration(alll_ctx* c, hipEvent_t* marks, int variant) {
         HIP_TRY(launch_apply_delta(c->b, s));
     } else if (c->grp) {
         HIP_TRY(launch_group_account(c->cv, c->b, *c->grp, s));
-        HIP_TRY(launch_group_resample(c->b, *c->grp, s));
+        HIP_TRY(launch_group_resample(c->b, *c->grp, c->grp_wbias, s));
     } else {
         HIP_TRY(launch_resample(c->cv, c->b, c->own_begin, c->own_end, false, s));
     }
@@ -699,6 +703,47 @@ int fill_stats(alll_ctx* c, alll_stats* st) {
     return ALLL_OK;
 }
 
+// Captured iterations hold LoopBuffers (and the group's pointers) by value: after a change of
+// either they are dropped, and the next launch batch captures them again.  Stream drained.
+void drop_graphs(alll_ctx* c) {
+    for (int v = 0; v < 3; ++v)
+        for (int u = 0; u < GRAPH_SIZES; ++u) {
+            if (c->graph_exec[v][u]) (void)hipGraphExecDestroy(c->graph_exec[v][u]);
+            if (c->graph[v][u]) (void)hipGraphDestroy(c->graph[v][u]);
+            c->graph_exec[v][u] = nullptr;
+            c->graph[v][u] = nullptr;
+        }
+    for (auto& g : c->rr_pre) {
+        if (g) (void)hipGraphExecDestroy(g);
+        g = nullptr;
+    }
+    for (hipGraphExec_t* g : {&c->rr_more, &c->rr_full, &c->rr_post}) {
+        if (*g) (void)hipGraphExecDestroy(*g);
+        *g = nullptr;
+    }
+    for (auto g : c->rr_graph) (void)hipGraphDestroy(g);
+    c->rr_graph.clear();
+}
+
+// Per-variable probabilities hook into the resample of the one-GPU loop only.
+int bias_supported(const alll_ctx* c) {
+    if ((c->opt.flags & ALLL_FLAG_REFERENCE_RNG) || c->b.rrng_mask)
+        return fail(ALLL_ERR_UNSUPPORTED, "variable thresholds: ALLL_FLAG_REFERENCE_RNG draws the reference's own "
+                                          "fair-coin stream");
+    if ((c->opt.flags & ALLL_FLAG_EXCHANGE_ALLREDUCE) || c->allreduce)
+        return fail(ALLL_ERR_UNSUPPORTED, "variable thresholds: ALLL_FLAG_EXCHANGE_ALLREDUCE resamples through the "
+                                          "delta exchange, which draws fair coins only");
+    bool zero_id = true;
+    for (int i = 0; i < 128; ++i) zero_id &= c->opt.comm_id[i] == 0;
+    if (c->world != 1 || c->comm || !zero_id)
+        return fail(ALLL_ERR_UNSUPPORTED, "variable thresholds: one GPU only (world %d%s)", c->world,
+                    zero_id ? "" : ", a communicator id");
+    if (c->opt.stream_batch != 0)
+        return fail(ALLL_ERR_UNSUPPORTED, "variable thresholds: the streaming solve (stream_batch %llu) is not covered",
+                    (unsigned long long)c->opt.stream_batch);
+    return ALLL_OK;
+}
+
 bool is_gfx950(int dev) {
     hipDeviceProp_t p;
     if (hipGetDeviceProperties(&p, dev) != hipSuccess) return false;
@@ -720,6 +765,12 @@ int ctx_launch_iterations(alll_ctx* c, uint64_t n) { return launch_iterations(c,
 void ctx_assignment_changed(alll_ctx* c) {
     c->hint_u = ~0ull;
     c->async_pending = false;
+}
+int ctx_bias_supported(alll_ctx* c) { return bias_supported(c); }
+void ctx_set_group_bias(alll_ctx* c, const uint32_t* thr, const uint32_t* wbias) {
+    c->b.thr = thr;
+    c->grp_wbias = wbias;
+    drop_graphs(c);
 }
 
 }  // namespace alll
@@ -1121,17 +1172,7 @@ int alll_destroy(alll_ctx* c) {
     if (!c) return ALLL_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (int v = 0; v < 3; ++v)
-        for (int u = 0; u < GRAPH_SIZES; ++u) {
-            if (c->graph_exec[v][u]) (void)hipGraphExecDestroy(c->graph_exec[v][u]);
-            if (c->graph[v][u]) (void)hipGraphDestroy(c->graph[v][u]);
-        }
-    for (auto& g : c->rr_pre)
-        if (g) (void)hipGraphExecDestroy(g);
-    if (c->rr_more) (void)hipGraphExecDestroy(c->rr_more);
-    if (c->rr_full) (void)hipGraphExecDestroy(c->rr_full);
-    if (c->rr_post) (void)hipGraphExecDestroy(c->rr_post);
-    for (auto g : c->rr_graph) (void)hipGraphDestroy(g);
+    drop_graphs(c);
     if (c->h_fp) (void)hipHostFree(c->h_fp);
     if (c->h_srr) (void)hipHostFree(c->h_srr);
     if (c->h_plan) (void)hipHostFree(c->h_plan);
@@ -1292,6 +1333,37 @@ int alll_set_assignment(alll_ctx* c, const uint8_t* in, uint64_t n) {
     for (uint32_t v = 0; v < c->n_vars; ++v)
         if (in[v]) w[v >> 5] |= 1u << (v & 31);
     return alll_set_assignment_words(c, w.data(), w.size());
+}
+
+int alll_set_var_thresholds(alll_ctx* c, const uint32_t* thr, uint64_t n) {
+    if (!c) return fail(ALLL_ERR_INVALID_ARG, "null context");
+    if (c->grp) return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: the context belongs to a group "
+                                                  "(alll_group_set_var_thresholds)");
+    int rc;
+    if ((rc = bias_supported(c))) return rc;
+    if (thr && n != c->n_vars)
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: %llu entries for %u variables", (unsigned long long)n,
+                    c->n_vars);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = read_state(c))) return rc;  // (drains the stream)
+    if (c->h_state->n_iter != 0)
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds are set before the first iteration (%llu made)",
+                    (unsigned long long)c->h_state->n_iter);
+    LoopBuffers& b = c->b;
+    if (thr && b.n_words) {
+        // the context's own copy, padded with zeros to whole words (k_resample_biased loads 16 per lane)
+        if (!c->d_thr && (rc = dalloc(c, &c->d_thr, (size_t)b.n_words * 32))) return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(c->d_thr, thr, (size_t)c->n_vars * 4, hipMemcpyHostToDevice));
+        b.thr = c->d_thr;
+    } else {
+        b.thr = nullptr;
+    }
+    drop_graphs(c);  // (none is captured before the first iteration; one would hold the old pointer)
+    HIP_TRY(launch_fill_words(b.A, b.n_words, b.n_vars, b.thr, b.seed, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    ctx_assignment_changed(c);
+    return ALLL_OK;
 }
 
 int alll_get_violated_mask(alll_ctx* c, uint64_t* out, uint64_t n_words) {

@@ -91,14 +91,40 @@ def read_dimacs(path: str):
     return int(v.value), offs, lits[: ln.value]
 
 
+# ------------------------------------------------ per-variable probabilities (alll.h)
+def var_thresholds(p) -> np.ndarray:
+    """Probabilities P(x_v = 1) -> the uint32 thresholds of Solver.set_thresholds
+    (alll_var_threshold per entry: 0 -> 0 and 1 -> 0xFFFFFFFF pin the variable)."""
+    p = np.atleast_1d(np.asarray(p, np.float64))
+    vals, inv = np.unique(p, return_inverse=True)  # (one call per distinct probability)
+    thr = np.zeros(vals.size, np.uint32)
+    L, t = N.lib(), ctypes.c_uint32()
+    for i, x in enumerate(vals.tolist()):
+        N.check(L.alll_var_threshold(x, ctypes.byref(t)), f"var_thresholds({x})")
+        thr[i] = t.value
+    return thr[inv].reshape(p.shape)
+
+
+def biased_initial_assignment(seed: int, n_vars: int, thr) -> np.ndarray:
+    """The biased initial fill for `seed` under thresholds thr, as n_vars bytes of 0/1 (host-only)."""
+    thr = np.ascontiguousarray(thr, np.uint32)
+    if thr.size != n_vars:
+        raise ValueError(f"{thr.size} thresholds for {n_vars} variables")
+    out = np.zeros(max(1, n_vars), np.uint8)
+    N.check(N.lib().alll_biased_initial_assignment(seed, n_vars, _p(thr, _u32p), _p(out, _u8p)),
+            "biased_initial_assignment")
+    return out[:n_vars]
+
+
 # ----------------------------------------------------------------------------- Solver
 class Solver:
-    """Owns one device solver context (alll_ctx)."""
+    """Owns one device solver context (alll_ctx).  probabilities: P(x_v = 1) per variable (0 and 1
+    pin the variable; set_probabilities), None = fair coins, the unbiased stream."""
 
     def __init__(self, n_vars: int, offsets, literals, seed: int = 1, max_iters: int = 0,
                  device: int = -1, n_threads: int = 1, rank: int = 0, world: int = 1,
                  comm_id: Optional[bytes] = None, flags: int = 0, grid_rounds: int = 0,
-                 exchange=None, stream_batch: int = 0, set_starts=None):
+                 exchange=None, stream_batch: int = 0, set_starts=None, probabilities=None):
         self._L = N.lib()
         self.n_vars = int(n_vars)
         self.offsets = np.ascontiguousarray(offsets, np.uint64)
@@ -126,6 +152,25 @@ class Solver:
         self._xfn = None
         if exchange is not None:
             self.set_host_exchange(exchange)
+        if probabilities is not None:
+            try:
+                self.set_probabilities(probabilities)
+            except Exception:
+                self.close()
+                raise
+
+    def set_probabilities(self, p):
+        """P(x_v = 1) per variable (n_vars entries; 0 and 1 pin the variable), or None for the
+        unbiased stream.  Before the first iteration only; rewrites the assignment (alll.h)."""
+        self.set_thresholds(None if p is None else var_thresholds(p))
+
+    def set_thresholds(self, thr):
+        """alll_set_var_thresholds: n_vars uint32 thresholds (var_thresholds), or None."""
+        if thr is None:
+            N.check(self._L.alll_set_var_thresholds(self._ctx, None, 0), "set_var_thresholds")
+            return
+        thr = np.ascontiguousarray(thr, np.uint32)
+        N.check(self._L.alll_set_var_thresholds(self._ctx, _p(thr, _u32p), thr.size), "set_var_thresholds")
 
     def set_host_exchange(self, exchange):
         """exchange(op, buf: numpy uint8 view, bytes_per_rank_or_total) -> None; see
@@ -472,6 +517,20 @@ class GroupSolver:
     def set_assignment_words(self, i: int, w):
         w = np.ascontiguousarray(w, np.uint32)
         N.check(self._L.alll_group_set_assignment_words(self._g, i, _p(w, _u32p), w.size), "group set_assignment")
+
+    def set_probabilities(self, i: int, p):
+        """Solver.set_probabilities for item i: it then computes what a Solver with seeds[i] and the
+        same probabilities computes.  Items that are one instance under different pinned variables
+        and solve(first_solved=True) make a cube portfolio."""
+        self.set_thresholds(i, None if p is None else var_thresholds(p))
+
+    def set_thresholds(self, i: int, thr):
+        """alll_group_set_var_thresholds: the item's n_vars uint32 thresholds, or None."""
+        if thr is None:
+            N.check(self._L.alll_group_set_var_thresholds(self._g, i, None, 0), "group set_var_thresholds")
+            return
+        thr = np.ascontiguousarray(thr, np.uint32)
+        N.check(self._L.alll_group_set_var_thresholds(self._g, i, _p(thr, _u32p), thr.size), "group set_var_thresholds")
 
     def layout(self) -> int:
         """Layout of the union: 0 generic CSR, k > 0 fixed width k."""

@@ -197,6 +197,29 @@ int alll_set_assignment(alll_ctx* ctx, const uint8_t* in, uint64_t n);
 int alll_get_assignment_words(alll_ctx* ctx, uint32_t* out, uint64_t n_words);
 int alll_set_assignment_words(alll_ctx* ctx, const uint32_t* in, uint64_t n_words);
 
+/* Per-variable resample probabilities and pinned variables.  thr[v] (n == n_vars
+ * entries, alll_var_threshold) gives variable v its own draw, at the initial fill and at every
+ * resample (round it = n_iterations - 1):
+ *   u(v, it) = Philox4x32-10(key = seed, ctr = {v >> 2, it lo, 1, it hi})[v & 3]
+ *   u0(v)    = Philox4x32-10(key = seed, ctr = {v >> 2, 0, 0xFFFFFFFE, 0})[v & 3]     (initial fill)
+ *   bit      = thr[v] == 0xFFFFFFFF ? 1 : (u < thr[v])
+ * (the four output words in Random123 order).  thr = 0 pins the variable to 0 and thr = 0xFFFFFFFF
+ * to 1: no resample changes it; any other value gives P(1) = thr / 2^32.  Counter word 2 (0 in the
+ * unbiased resample, 0xFFFFFFFF in the unbiased fill) keeps these draws disjoint from the unbiased
+ * stream: thr = 2^31 everywhere is a fair coin, but it is NOT the stream of a context without
+ * thresholds.  A variable that occurs twice in a clause is drawn once.
+ * Allowed only before the first iteration (n_iterations == 0), else ALLL_ERR_INVALID_ARG, as a
+ * wrong n.  The call copies the thresholds (no caller pointer is kept), rewrites the assignment
+ * with the biased fill and takes effect from the next iteration on; thr == NULL restores the
+ * unbiased stream and the unbiased fill.  alll_set_assignment* afterwards is not checked against
+ * the pins: a pinned variable keeps whatever value the caller gives it.  A clause whose literals
+ * are all pinned false can never be satisfied: the loop then runs to max_iters (not detected on
+ * the host).  Supported: any n_threads, every flag that does not change results, one GPU.
+ * ALLL_ERR_UNSUPPORTED, before any device work (the message names the reason): a context created
+ * with ALLL_FLAG_REFERENCE_RNG, ALLL_FLAG_EXCHANGE_ALLREDUCE, world != 1 or a non-zero comm_id, or
+ * stream_batch != 0.  (No reference counterpart: the reference draws fair coins.) */
+int alll_set_var_thresholds(alll_ctx* ctx, const uint32_t* thr, uint64_t n);
+
 /* Introspection of the last iteration (parity tests): violated bitmask of the last eval
  * pass (ceil(n_clauses/64) words) and the MIS picked from it (ascending clause order). */
 int alll_get_violated_mask(alll_ctx* ctx, uint64_t* out, uint64_t n_words);
@@ -334,6 +357,13 @@ int alll_group_get_stats(alll_group* g, uint64_t item, alll_stats* stats);
  * item is refused (ALLL_ERR_INVALID_ARG): a solved item is final. */
 int alll_group_get_assignment_words(alll_group* g, uint64_t item, uint32_t* out, uint64_t n_words);
 int alll_group_set_assignment_words(alll_group* g, uint64_t item, const uint32_t* in, uint64_t n_words);
+/* alll_set_var_thresholds for one item (n == the item's n_vars; v is local to the item and the key
+ * is seeds[item]): item i then behaves exactly as a context created from probs[i] with seeds[i] and
+ * given the same thresholds; items without thresholds keep the unbiased stream bit for bit.  Only
+ * before the group's first iteration; rewrites that item's words only.  With
+ * ALLL_GROUP_FIRST_SOLVED, items that are one instance under different pinned variables make a
+ * cube portfolio: the first cube solved wins. */
+int alll_group_set_var_thresholds(alll_group* g, uint64_t item, const uint32_t* thr, uint64_t n);
 /* alll_layout / alll_eval_kernel of the union. */
 int alll_group_layout(alll_group* g);
 const char* alll_group_eval_kernel(alll_group* g);
@@ -384,6 +414,14 @@ int alll_plan_multi_gpu(uint64_t n_clauses, uint64_t n_literals, uint32_t n_vars
  * form = Philox4x32-10(key=seed, ctr={w, 0, 0xFFFFFFFF, 0}).x); used by the compatibility
  * VariablesArray (replaces the random_device fill of VariablesArray.h:23-34). */
 int alll_initial_assignment(uint64_t seed, uint32_t n_vars, uint8_t* out);
+
+/* The threshold of probability p for alll_set_var_thresholds: p = 0 -> 0 (pinned to 0), p = 1 ->
+ * 0xFFFFFFFF (pinned to 1), else min(floor(p * 2^32), 0xFFFFFFFE) (so p < 2^-32 pins to 0 and no
+ * p < 1 pins to 1); NaN or p outside [0, 1]: ALLL_ERR_INVALID_ARG. */
+int alll_var_threshold(double p, uint32_t* thr);
+/* The biased initial fill (alll_set_var_thresholds, u0) for `seed` and n_vars thresholds, as
+ * n_vars bytes of 0/1. */
+int alll_biased_initial_assignment(uint64_t seed, uint32_t n_vars, const uint32_t* thr, uint8_t* out);
 
 /* The reference's own initial assignment (VariablesArray.h:23-34) in the reference-RNG mode
  * (ALLL_FLAG_REFERENCE_RNG): `rd_state` is the random_device stand-in's state
