@@ -4,10 +4,21 @@ mask_to_list, lfmis / rr_mis, clause_vars) -- nothing of the code under test.
 
     u(v, it) = Philox4x32-10(key = seed, ctr = {v >> 2, it lo, 1, it hi})[v & 3]
     u0(v)    = Philox4x32-10(key = seed, ctr = {v >> 2, 0, 0xFFFFFFFE, 0})[v & 3]     (initial fill)
-    bit      = thr[v] == 0xFFFFFFFF ? 1 : (u < thr[v])"""
+    bit      = thr[v] == 0xFFFFFFFF ? 1 : (u < thr[v])
+
+Below the stream: the CPU loop over it (reference, follow), and the cases of
+tests/test_gpu_bias_blocks.py, whose sizes leave the first workgroup of the biased kernels (a resample
+workgroup holds 4096 variables = 128 assignment words, a fill workgroup 8192 variables = 256 words,
+a word of a group's per-word bits 1024 variables = 32 words).  A case is computed once per process and
+shared, read-only, by the CPU module that pins its facts (tests/test_bias_cases.py) and the GPU tests."""
+import functools
+
 import numpy as np
 
+from group_cases import compose, oracle_step
+
 PIN1 = 0xFFFFFFFF
+RESAMPLE_WG_WORDS, FILL_WG_WORDS, WBIAS_WORDS = 128, 256, 32  # assignment words per workgroup / per-word-bit word
 
 
 def biased_bits(o, seed, it, vs, thr):
@@ -58,3 +69,250 @@ def mixed_thresholds(n, seed, must=()):
         if v < n:
             thr[v] = t
     return thr
+
+
+# ---------------------------------------------------------------------------------------------
+# The loop on the CPU and a solver followed along it
+
+
+def reference(o, n, offs, lits, seed, thr, iters, T=1, A0=None):
+    """The biased loop on the CPU: the initial assignment (the biased fill, or A0 when one is imposed)
+    and, per iteration, (violated mask, |U|, MIS, its literal count, next assignment); ends after an
+    iteration that finds nothing violated."""
+    first = biased_init(o, seed, n, thr) if A0 is None else np.array(A0, np.uint32)
+    A = first.copy()
+    rows = []
+    for it in range(iters):
+        vm, U, M, B = biased_step(o, n, offs, lits, A, seed, it, thr, T)
+        Mi = M.astype(np.int64)
+        rows.append((vm, int(U.size), M, int((offs[Mi + 1] - offs[Mi]).sum()), B))
+        if U.size == 0:
+            break
+        A = B
+    return first, rows
+
+
+def unbiased_reference(o, n, offs, lits, seed, iters):
+    """reference() for fair coins: the oracle's own fill and step (group_cases.oracle_step), the rows
+    in the same shape."""
+    first = o.init_assignment(seed, n)
+    A = first.copy()
+    rows = []
+    for it in range(iters):
+        _, vm = o.eval_mask(offs, lits, A)
+        U, M, B = oracle_step(o, n, offs, lits, A, seed, it)
+        Mi = M.astype(np.int64)
+        rows.append((vm, int(U.size), M, int((offs[Mi + 1] - offs[Mi]).sum()), B))
+        if U.size == 0:
+            break
+        A = B
+    return first, rows
+
+
+def follow(s, A0, rows, what):
+    """Every run(1) of solver s against the reference rows: assignment words, violated mask, MIS,
+    n_resamples and sum_mis_size."""
+    np.testing.assert_array_equal(s.assignment_words(), A0, err_msg=f"{what}: initial assignment")
+    sum_mis = n_res = 0
+    for it, (vm, nu, M, nlit, B) in enumerate(rows):
+        st = s.run(1)
+        assert (st["n_iterations"], st["n_violated"], st["solved"]) == (it + 1, nu, int(nu == 0)), (what, it)
+        np.testing.assert_array_equal(s.violated_mask(), vm, err_msg=f"{what}: violated mask, iteration {it}")
+        if nu:
+            np.testing.assert_array_equal(s.mis(), M, err_msg=f"{what}: MIS, iteration {it}")
+            sum_mis += M.size
+            n_res += nlit
+        assert (st["sum_mis_size"], st["n_resamples"]) == (sum_mis, n_res), (what, it)
+        np.testing.assert_array_equal(s.assignment_words(), B, err_msg=f"{what}: assignment after iteration {it}")
+
+
+def stats_after(rows, k):
+    """The statistics after k iterations of a reference that is unsolved through all of them."""
+    done = rows[:k]
+    assert len(done) == k and all(r[1] > 0 for r in done)
+    return dict(n_iterations=k, n_violated=done[-1][1], sum_mis_size=sum(r[2].size for r in done),
+                n_resamples=sum(r[3] for r in done), solved=0)
+
+
+def sizes(rows):
+    """(|U|, |M|) per iteration."""
+    return [(r[1], int(r[2].size)) for r in rows]
+
+
+# ---------------------------------------------------------------------------------------------
+# The cases of tests/test_gpu_bias_blocks.py
+
+
+def cover_all(n):
+    """n / 3 clauses (x_3i | x_3i+1 | x_3i+2), all literals positive: from the all-false assignment every
+    clause is violated and in the MIS, so every variable is drawn in iteration 0."""
+    assert n % 3 == 0
+    return np.arange(n // 3 + 1, dtype=np.uint64) * np.uint64(3), np.arange(n, dtype=np.uint32) << np.uint32(1)
+
+
+def _ksat(gen, n, m, k):
+    from alllsatisfiabilitysolver_amd import generate_ksat
+
+    return generate_ksat(gen, n, m, k)
+
+
+def _frozen(case):
+    """A shared case is left unchanged: its arrays are read-only."""
+    def freeze(x):
+        if isinstance(x, np.ndarray):
+            x.flags.writeable = False
+        elif isinstance(x, (tuple, list)):
+            for y in x:
+                freeze(y)
+        elif isinstance(x, dict):
+            for y in x.values():
+                freeze(y)
+    freeze(case)
+    return case
+
+
+# pins and a bias on both sides of the resample workgroups' edges (4096 variables), of the fill's
+# (8192) and on the last variable
+BLOCKS_MUST = ((4095, 0), (4096, PIN1), (8191, PIN1), (8192, 0), (16383, 0x40000000), (16384, PIN1), (20002, 0))
+
+
+@functools.lru_cache(maxsize=None)
+def blocks_case():
+    """1. n = 20003 (no multiple of 32; 626 words: five resample workgroups, three of the fill),
+    m = 80000, k = 3: ten iterations."""
+    import oracle as o
+
+    n, seed = 20003, 17
+    offs, lits = _ksat(11, n, 80000, 3)
+    thr = mixed_thresholds(n, 7, must=BLOCKS_MUST)
+    A0, rows = reference(o, n, offs, lits, seed, thr, 10)
+    return _frozen(dict(n=n, offs=offs, lits=lits, seed=seed, thr=thr, A0=A0, rows=rows))
+
+
+@functools.lru_cache(maxsize=None)
+def cover_all_case():
+    """2. cover_all(20001) (625 words and one variable) from the all-false assignment: four iterations."""
+    import oracle as o
+
+    n, seed = 20001, 23
+    offs, lits = cover_all(n)
+    thr = mixed_thresholds(n, 21)
+    A0, rows = reference(o, n, offs, lits, seed, thr, 4, A0=np.zeros((n + 31) // 32, np.uint32))
+    return _frozen(dict(n=n, offs=offs, lits=lits, seed=seed, thr=thr, A0=A0, rows=rows))
+
+
+WRAP_ITERS, WRAP_STOPS = 260, (250, 254, 255, 256, 257, 260)
+
+
+def _small_instance():
+    n = 5003
+    return n, *_ksat(12, n, 20000, 3), 18, mixed_thresholds(n, 8)
+
+
+@functools.lru_cache(maxsize=None)
+def wrap_case():
+    """3. n = 5003, m = 20000: 260 iterations, across the wrap of the 8-bit cover stamps."""
+    import oracle as o
+
+    n, offs, lits, seed, thr = _small_instance()
+    A0, rows = reference(o, n, offs, lits, seed, thr, WRAP_ITERS)
+    return _frozen(dict(n=n, offs=offs, lits=lits, seed=seed, thr=thr, A0=A0, rows=rows))
+
+
+@functools.lru_cache(maxsize=None)
+def rr_case(T):
+    """4. The instance of wrap_case under the round robin of T sets: eight iterations."""
+    import oracle as o
+
+    n, offs, lits, seed, thr = _small_instance()
+    A0, rows = reference(o, n, offs, lits, seed, thr, 8, T=T)
+    return _frozen(dict(n=n, offs=offs, lits=lits, seed=seed, thr=thr, A0=A0, rows=rows, T=T))
+
+
+def repeated_in_mis(offs, lits, rows):
+    """MIS clauses, over all rows, in which a variable occurs more than once."""
+    k = 0
+    for r in rows:
+        for c in r[2].astype(np.int64).tolist():
+            v = lits[int(offs[c]):int(offs[c + 1])] >> 1
+            k += int(np.unique(v).size < v.size)
+    return k
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_case():
+    """5. Mixed widths 1-9 with repeated variables, n = 9001 (282 words: three resample workgroups,
+    two of the fill): eight iterations, or until solved."""
+    import oracle as o
+    from alllsatisfiabilitysolver_amd import generate_mixed
+
+    n, seed = 9001, 15
+    offs, lits = generate_mixed(5, n, 20000, 1, 9)
+    thr = mixed_thresholds(n, 3)
+    A0, rows = reference(o, n, offs, lits, seed, thr, 8)
+    return _frozen(dict(n=n, offs=offs, lits=lits, seed=seed, thr=thr, A0=A0, rows=rows))
+
+
+# (n_vars, clauses, width, generator seed, seed of mixed_thresholds or None) per item, in this order
+GROUP_ITEMS = ((1500, 6000, 3, 40, None), (5003, 20000, 3, 41, 31), (33, 20, 2, 42, 32), (4097, 16400, 3, 43, None),
+               (9001, 36000, 3, 44, 33))
+GROUP_SEEDS = (70, 71, 72, 73, 74)
+GROUP_STEPS = 6
+
+
+def word_ranges(items):
+    """Per item of the union (group_cases.compose): ((first, last) assignment word, (first, last) word of
+    the per-word bits, (first, last) resample workgroup)."""
+    out = []
+    for p in compose(items)[3]:
+        w0, w1 = p["word_base"], p["word_base"] + p["n_words"] - 1
+        out.append(((w0, w1), (w0 // WBIAS_WORDS, w1 // WBIAS_WORDS), (w0 // RESAMPLE_WG_WORDS, w1 // RESAMPLE_WG_WORDS)))
+    return out
+
+
+def _item_reference(o, item, seed, thr, steps):
+    if thr is None:
+        return unbiased_reference(o, *item, seed, steps)
+    return reference(o, *item, seed, thr, steps)
+
+
+@functools.lru_cache(maxsize=None)
+def group_case(variant="table"):
+    """6. Five items whose words straddle the resample workgroups and the words of the per-word bits;
+    items 1, 2 and 4 have thresholds.  "table": GROUP_ITEMS as they stand (item 2 is 2-SAT among 3-SAT
+    items, so the union is laid out as generic CSR), six steps.  Three steps each: "ragged", item 2 is
+    generate_mixed(5, 300, 700, 1, 5); "fixed", item 2 is 3-SAT (33 variables, 140 clauses), so the
+    union has the fixed-width layout.  -> items, seeds, thresholds (None: unbiased), per item (A0, rows)."""
+    import oracle as o
+    from alllsatisfiabilitysolver_amd import generate_mixed
+
+    items = [(n, *_ksat(g, n, m, k)) for n, m, k, g, _ in GROUP_ITEMS]
+    thrs = [None if t is None else mixed_thresholds(n, t) for n, _, _, _, t in GROUP_ITEMS]
+    if variant == "ragged":
+        items[2] = (300, *generate_mixed(5, 300, 700, 1, 5))
+        thrs[2] = mixed_thresholds(300, GROUP_ITEMS[2][4])
+    elif variant == "fixed":
+        items[2] = (33, *_ksat(GROUP_ITEMS[2][3], 33, 140, 3))
+    else:
+        assert variant == "table"
+    steps = GROUP_STEPS if variant == "table" else 3
+    refs = [_item_reference(o, it, s, t, steps) for it, s, t in zip(items, GROUP_SEEDS, thrs)]
+    return _frozen(dict(items=items, seeds=list(GROUP_SEEDS), thrs=thrs, refs=refs, steps=steps))
+
+
+@functools.lru_cache(maxsize=None)
+def group_item4_unbiased():
+    """6. Item 4 of group_case after its thresholds were taken back: the oracle's unbiased run, three steps."""
+    import oracle as o
+
+    g = group_case()
+    return _frozen(unbiased_reference(o, *g["items"][4], g["seeds"][4], 3))
+
+
+@functools.lru_cache(maxsize=None)
+def blocks_unbiased():
+    """7. blocks_case without thresholds: the oracle's unbiased run, four steps."""
+    import oracle as o
+
+    c = blocks_case()
+    return _frozen(unbiased_reference(o, c["n"], c["offs"], c["lits"], c["seed"], 4))

@@ -8,7 +8,7 @@ import functools
 import numpy as np
 import pytest
 
-from bias_cases import PIN1, biased_init, biased_step, mixed_thresholds
+from bias_cases import PIN1, follow, mixed_thresholds, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -24,38 +24,6 @@ def gpu(native):
     if device_count() == 0:
         pytest.fail("no GPU visible: the gpu tests must run on an MI355X")
     return True
-
-
-def reference(o, n, offs, lits, seed, thr, iters, T=1):
-    """The biased loop on the CPU: the initial assignment and, per iteration, (violated mask, |U|, MIS,
-    its literal count, next assignment); ends after an iteration that finds nothing violated."""
-    A = biased_init(o, seed, n, thr)
-    rows = []
-    for it in range(iters):
-        vm, U, M, B = biased_step(o, n, offs, lits, A, seed, it, thr, T)
-        Mi = M.astype(np.int64)
-        rows.append((vm, int(U.size), M, int((offs[Mi + 1] - offs[Mi]).sum()), B))
-        if U.size == 0:
-            break
-        A = B
-    return biased_init(o, seed, n, thr), rows
-
-
-def follow(s, A0, rows, what):
-    """Every run(1) of solver s against the reference rows: assignment words, violated mask, MIS,
-    n_resamples and sum_mis_size."""
-    np.testing.assert_array_equal(s.assignment_words(), A0, err_msg=f"{what}: initial assignment")
-    sum_mis = n_res = 0
-    for it, (vm, nu, M, nlit, B) in enumerate(rows):
-        st = s.run(1)
-        assert (st["n_iterations"], st["n_violated"], st["solved"]) == (it + 1, nu, int(nu == 0)), (what, it)
-        np.testing.assert_array_equal(s.violated_mask(), vm, err_msg=f"{what}: violated mask, iteration {it}")
-        if nu:
-            np.testing.assert_array_equal(s.mis(), M, err_msg=f"{what}: MIS, iteration {it}")
-            sum_mis += M.size
-            n_res += nlit
-        assert (st["sum_mis_size"], st["n_resamples"]) == (sum_mis, n_res), (what, it)
-        np.testing.assert_array_equal(s.assignment_words(), B, err_msg=f"{what}: assignment after iteration {it}")
 
 
 SPECIAL = [(31, 0), (32, PIN1), (63, PIN1), (64, 0), (202, 0x40000000), (30, 0xC0000000), (33, 1), (62, 0xFFFFFFFE)]
