@@ -37,8 +37,10 @@ $(SRC)/alll_host.o: $(SRC)/alll_host.cpp include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 # batches of LDS-resident instances: kernel, host-only planner, device set-up
+# (SMALL_REMARKS=-Rpass-analysis=kernel-resource-usage prints the registers, scratch and LDS of both
+# instantiations of the batch kernel: DESIGN.md §4.6)
 $(SRC)/alll_small.o: $(SRC)/alll_small.hip $(SRC)/alll_small.h $(SRC)/alll_batch.h $(SRC)/alll_philox.h include/alll.h
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+	$(HIPCC) $(HIPFLAGS) $(SMALL_REMARKS) -c -o $@ $<
 
 $(SRC)/alll_batch.o: $(SRC)/alll_batch.cpp $(SRC)/alll_batch.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<

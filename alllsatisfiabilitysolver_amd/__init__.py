@@ -6,7 +6,8 @@ include/alll.h (liballl.so).  This package is the Python front-end of that libra
 """
 from ._native import AlllError, build, lib  # noqa: F401
 from .solver import (BatchSolver, Clause, GroupSolver, SATInstance, Solver, Statistics, VariablesArray,  # noqa: F401
-                     batch_fits, solve_portfolio, var_thresholds, biased_initial_assignment,
+                     batch_fits, solve_portfolio, solve_cubes, cube_thresholds, pinned_conflict, var_thresholds,
+                     biased_initial_assignment,
                      assignment_digest, comm_unique_id, device_count, generate_ksat, generate_mixed, gloo_exchange,
                      parse_dimacs,
                      read_dimacs, shard_plan, plan_multi_gpu)

@@ -62,7 +62,7 @@ EXPORTED = [
     "alll_group_get_assignment_words", "alll_group_set_assignment_words", "alll_group_layout",
     "alll_group_eval_kernel",
     "alll_var_threshold", "alll_biased_initial_assignment", "alll_set_var_thresholds",
-    "alll_group_set_var_thresholds",
+    "alll_group_set_var_thresholds", "alll_batch_set_var_thresholds", "alll_pinned_conflict",
 ]
 
 
@@ -205,6 +205,8 @@ _SIGS = {
     "alll_biased_initial_assignment": ([ctypes.c_uint64, ctypes.c_uint32, _u32p, _u8p], ctypes.c_int),
     "alll_set_var_thresholds": ([_vp, _u32p, ctypes.c_uint64], ctypes.c_int),
     "alll_group_set_var_thresholds": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_batch_set_var_thresholds": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_pinned_conflict": ([ctypes.POINTER(Problem), _u32p, ctypes.c_uint64, _u64p], ctypes.c_int),
 }
 
 _lib = None
@@ -224,6 +226,8 @@ def lib():
             raise ImportError(f"{LIB_PATH} not built: run `make` (or __graft_entry__.build())")
         L = ctypes.CDLL(LIB_PATH)
         for name, (args, res) in _SIGS.items():
+            if os.environ.get("ALLL_LIB_AB") and not hasattr(L, name):
+                continue  # (an older build under A/B timing lacks the newest entry points)
             f = getattr(L, name)
             f.argtypes = args
             f.restype = res

@@ -84,6 +84,13 @@ SmallLds small_lds_layout(uint32_t max_vars, uint32_t max_clauses, uint32_t max_
     return l;
 }
 
+SmallLds small_lds_layout(uint32_t max_vars, uint32_t max_clauses, uint32_t max_lits, uint32_t* thr_at) {
+    SmallLds l = small_lds_layout(max_vars, max_clauses, max_lits);
+    *thr_at = l.bytes;  // (every array ends at a multiple of 16; never 0: the control words come before)
+    l.bytes += round_up(4 * max_vars, 16);
+    return l;
+}
+
 int plan_batch(const alll_problem* probs, const uint64_t* seeds, uint64_t n_items, const alll_options& opt,
                BatchPlan& p) {
     if (!probs || !seeds) return fail(p, ALLL_ERR_INVALID_ARG, "batch: null argument");

@@ -21,7 +21,7 @@ struct SmallItem {
     uint32_t m, n_lits;
     uint32_t lits_at, offs_at;  // first element of the problem in the literal / offset pool
     uint32_t a_at;              // first word of the item's assignment in the assignment pool
-    uint32_t pad;
+    uint32_t pad;               // the planner's 0; the runtime sets 1 while the item has thresholds (§4.8)
 };
 static_assert(sizeof(SmallItem) == 40, "SmallItem");
 
@@ -68,6 +68,16 @@ struct BatchPlan {
 
 bool batch_fits(uint32_t n_vars, uint64_t n_clauses, uint64_t n_literals);
 SmallLds small_lds_layout(uint32_t max_vars, uint32_t max_clauses, uint32_t max_lits);
+// Per-variable thresholds of a batch with a biased item: the same layout followed
+// by u32[max variables, rounded up to 4] at *thr_at; bytes includes it.  The thresholds are
+// LDS-resident when this layout is within SMALL_LDS_BUDGET, else the kernel reads them from global
+// memory and keeps the layout above.
+constexpr uint32_t SMALL_LDS_BUDGET = 160u * 1024u;
+SmallLds small_lds_layout(uint32_t max_vars, uint32_t max_clauses, uint32_t max_lits, uint32_t* thr_at);
+inline bool small_thr_fits_lds(uint32_t max_vars, uint32_t max_clauses, uint32_t max_lits) {
+    uint32_t at;
+    return small_lds_layout(max_vars, max_clauses, max_lits, &at).bytes <= SMALL_LDS_BUDGET;
+}
 // Validation (options, then every item: the message names the item's index), deduplication by
 // pointer and size, 16-bit packing, LDS layout and workgroup size.
 int plan_batch(const alll_problem* probs, const uint64_t* seeds, uint64_t n_items, const alll_options& opt,

@@ -56,6 +56,13 @@ uint32_t serial_max_knob() {
     return (uint32_t)std::min<unsigned long long>(strtoull(e, nullptr, 10), 64);
 }
 
+// ALLL_BATCH_THR_GLOBAL=1: a biased batch reads its thresholds from global memory also where they
+// would fit the LDS (tuning, tests).  The results do not depend on it.
+bool thr_global_knob() {
+    const char* e = getenv("ALLL_BATCH_THR_GLOBAL");
+    return e && *e && strtoull(e, nullptr, 10) != 0;
+}
+
 }  // namespace
 
 struct alll_batch {
@@ -67,6 +74,10 @@ struct alll_batch {
     SmallBatch d{};
     SmallState* h_state = nullptr;  // pinned, n_items
     std::vector<void*> allocs;
+    // per-variable thresholds: the pool is allocated at the first item that gets some
+    uint32_t max_vars = 0, max_clauses = 0, max_lits = 0, a_words = 0;
+    bool thr_global = false;      // ALLL_BATCH_THR_GLOBAL: never the LDS copy
+    std::vector<uint8_t> biased;  // per item
 };
 
 namespace {
@@ -175,6 +186,11 @@ int alll_batch_create(const alll_problem* probs, const uint64_t* seeds, uint64_t
     b->d.threads = plan.threads;
     b->d.lds = plan.lds;
     b->d.serial_max = serial_max_knob();
+    b->thr_global = thr_global_knob();
+    b->max_vars = plan.max_vars;
+    b->max_clauses = plan.max_clauses;
+    b->max_lits = plan.max_lits;
+    b->a_words = plan.a_words;
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
         return bail(fail(ALLL_ERR_HIP, "hipStreamCreate failed"));
     if (hipHostMalloc((void**)&b->h_state, sizeof(SmallState) * n_items, 0) != hipSuccess)
@@ -270,6 +286,59 @@ int alll_batch_set_assignment_words(alll_batch* b, uint64_t item, const uint32_t
     if (!w.empty() && (it.n_vars & 31)) w.back() &= (1u << (it.n_vars & 31)) - 1u;
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (it.n_words) HIP_TRY(hipMemcpy(b->d.A + it.a_at, w.data(), it.n_words * 4ull, hipMemcpyHostToDevice));
+    return ALLL_OK;
+}
+
+int alll_batch_set_var_thresholds(alll_batch* b, uint64_t item, const uint32_t* thr, uint64_t n) {
+    if (!b) return fail(ALLL_ERR_INVALID_ARG, "null batch");
+    if (item >= b->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, b->d.n_items);
+    SmallItem& it = b->items[item];
+    if (thr && n != it.n_vars)
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: %llu entries for the %u variables of item %llu",
+                    (unsigned long long)n, it.n_vars, (unsigned long long)item);
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    SmallState s;
+    HIP_TRY(hipMemcpy(&s, b->d.states + item, sizeof s, hipMemcpyDeviceToHost));
+    if (s.n_iter != 0)
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds are set before the item's first iteration (%llu made)",
+                    (unsigned long long)s.n_iter);
+    const bool on = thr && it.n_words;
+    // ---- the thresholds into the pool (item i's at 32 * a_at, zeros up to its whole words), the item's flag
+    if (on && !b->d.thr) {
+        void* q = nullptr;
+        const size_t bytes = std::max<size_t>((size_t)b->a_words * 128, 16);
+        if (hipMalloc(&q, bytes) != hipSuccess) return fail(ALLL_ERR_OOM, "hipMalloc(%zu bytes) failed", bytes);
+        b->allocs.push_back(q);
+        HIP_TRY(hipMemset(q, 0, bytes));
+        b->d.thr = static_cast<const uint32_t*>(q);
+        b->biased.assign(b->d.n_items, 0);
+    }
+    if (on)
+        HIP_TRY(hipMemcpy(const_cast<uint32_t*>(b->d.thr) + 32ull * it.a_at, thr, (size_t)it.n_vars * 4, hipMemcpyHostToDevice));
+    if (b->d.thr) {
+        it.pad = on ? 1u : 0u;
+        b->biased[item] = on;
+        HIP_TRY(hipMemcpy(const_cast<SmallItem*>(b->d.items) + item, &it, sizeof it, hipMemcpyHostToDevice));
+    }
+    // ---- the item's words again: the biased fill, or its unbiased one
+    if (it.n_words) {
+        std::vector<uint8_t> bits(it.n_vars);
+        if (int rc = on ? alll_biased_initial_assignment(it.seed, it.n_vars, thr, bits.data())
+                        : alll_initial_assignment(it.seed, it.n_vars, bits.data()))
+            return rc;
+        std::vector<uint32_t> w(it.n_words, 0u);
+        for (uint32_t v = 0; v < it.n_vars; ++v) w[v >> 5] |= (uint32_t)bits[v] << (v & 31);
+        HIP_TRY(hipMemcpy(b->d.A + it.a_at, w.data(), it.n_words * 4ull, hipMemcpyHostToDevice));
+    }
+    // ---- the launch choice: the biased instantiation while any item has thresholds; they are
+    // LDS-resident when the batch's layout with them fits the budget
+    b->d.biased = std::find(b->biased.begin(), b->biased.end(), 1) != b->biased.end();
+    uint32_t at = 0;
+    const SmallLds with = small_lds_layout(b->max_vars, b->max_clauses, b->max_lits, &at);
+    const bool in_lds = !b->thr_global && with.bytes <= SMALL_LDS_BUDGET;
+    b->d.thr_lds = in_lds ? at : 0;
+    b->d.lds_thr_bytes = with.bytes;
     return ALLL_OK;
 }
 

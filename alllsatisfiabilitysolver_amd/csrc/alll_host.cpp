@@ -514,6 +514,53 @@ int alll_biased_initial_assignment(uint64_t seed, uint32_t n_vars, const uint32_
     return ALLL_OK;
 }
 
+int alll_pinned_conflict(const alll_problem* prob, const uint32_t* thr, uint64_t n, uint64_t* clause) {
+    if (!prob || !clause || (!thr && n)) {
+        g_host_err = "pinned conflict: null argument";
+        return ALLL_ERR_INVALID_ARG;
+    }
+    if (n != prob->n_vars) {
+        g_host_err = "pinned conflict: " + std::to_string(n) + " thresholds for " + std::to_string(prob->n_vars) + " variables";
+        return ALLL_ERR_INVALID_ARG;
+    }
+    const uint64_t m = prob->n_clauses;
+    if (m && !prob->offsets) {
+        g_host_err = "pinned conflict: null offsets";
+        return ALLL_ERR_INVALID_ARG;
+    }
+    if (m && prob->offsets[0] != 0) {
+        g_host_err = "pinned conflict: offsets[0] != 0";
+        return ALLL_ERR_BAD_INPUT;
+    }
+    for (uint64_t c = 0; c < m; ++c)
+        if (prob->offsets[c + 1] < prob->offsets[c]) {
+            g_host_err = "pinned conflict: offsets decrease at " + std::to_string(c);
+            return ALLL_ERR_BAD_INPUT;
+        }
+    const uint64_t L = m ? prob->offsets[m] : 0;
+    if (L && !prob->literals) {
+        g_host_err = "pinned conflict: null literals";
+        return ALLL_ERR_INVALID_ARG;
+    }
+    for (uint64_t j = 0; j < L; ++j)
+        if ((prob->literals[j] >> 1) >= prob->n_vars) {
+            g_host_err = "pinned conflict: literal " + std::to_string(prob->literals[j]) + " at position " +
+                         std::to_string(j) + " exceeds n_vars " + std::to_string(prob->n_vars);
+            return ALLL_ERR_LITERAL_RANGE;
+        }
+    uint64_t first = m;
+    for (uint64_t c = 0; c < m && first == m; ++c) {
+        bool dead = true;
+        for (uint64_t j = prob->offsets[c]; j < prob->offsets[c + 1] && dead; ++j) {
+            const uint32_t l = prob->literals[j];
+            dead = thr[l >> 1] == ((l & 1u) ? 0xFFFFFFFFu : 0u);
+        }
+        if (dead) first = c;
+    }
+    *clause = first;
+    return ALLL_OK;
+}
+
 int alll_dimacs_parse(const char* buf, uint64_t len, uint32_t* n_vars, uint64_t* n_clauses,
                       uint64_t* offsets, uint32_t* literals, uint64_t* n_literals) {
     if (!buf && len) return ALLL_ERR_INVALID_ARG;

@@ -18,16 +18,21 @@ struct SmallBatch {
     uint32_t threads;   // workgroup size
     uint32_t serial_max;  // violated sets up to this size (<= 64) take the one-wave serial greedy, 0: never
     SmallLds lds;
+    // per-variable thresholds (alll_batch_set_var_thresholds)
+    const uint32_t* thr;     // the pool: item i's thresholds at 32 * a_at, zero-padded to its words; null until the first call
+    uint32_t thr_lds;        // byte offset of the LDS-resident thresholds behind lds, 0: the kernel reads the pool
+    uint32_t lds_thr_bytes;  // dynamic LDS with them
+    bool biased;             // an item has thresholds: the biased instantiation is launched
 };
 
-// the kernel's dynamic LDS attribute (on the batch's device, before its first slice)
+// the dynamic LDS attribute of both instantiations of the kernel (on the batch's device, before its first slice)
 hipError_t small_prepare();
 // initial assignment of every item: word w = Philox(seed, {w, 0, 0xFFFFFFFF, 0}).x, tail cleared
 hipError_t launch_small_init(const SmallBatch& b, hipStream_t s);
 // solve = true: limit_eval = limit_nores = value (alll_solve's cap); false: limit_eval = n_iter +
 // value, limit_nores = none (alll_run); a stop at limit_nores is lifted either way
 hipError_t launch_small_limits(const SmallBatch& b, bool solve, uint64_t value, hipStream_t s);
-// one slice: every unfinished item runs at most `slice` iterations
+// one slice: every unfinished item runs at most `slice` iterations (b.biased: the instantiation with thresholds)
 hipError_t launch_small_slice(const SmallBatch& b, uint32_t slice, hipStream_t s);
 
 }  // namespace alll

@@ -12,6 +12,8 @@
 // with workgroup barriers only, and writes the assignment and the state back.  No global atomic,
 // no spin-wait, no grid barrier: every loop is bounded (the slice; LFMIS rounds <= violated
 // clauses), and the host relaunches until every item is done.  Integer / bit work only.
+// Two instantiations of one body: k_small for a batch without per-variable thresholds, k_small_biased
+// for a batch in which at least one item has some.
 #include "alll_small.h"
 #include "alll_philox.h"
 
@@ -33,25 +35,51 @@ __device__ __forceinline__ uint32_t lane_rank(unsigned long long mask) {  // set
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
-// clause [j0, j1) joins the MIS: its variables are covered (claim word 0) and resampled
+// Per-variable thresholds of a biased batch: the item's own, LDS-resident (lds)
+// when the batch's layout with them fits, else read from the pool in global memory (glb); `on` is
+// the item's flag (SmallItem::pad), uniform over the workgroup.
+struct SmallThr {
+    const uint32_t* lds;
+    const uint32_t* __restrict__ glb;
+    bool on, in_lds;
+};
+
+// clause [j0, j1) joins the MIS: its variables are covered (claim word 0) and resampled.  BIASED and
+// an item with thresholds: variable v draws element v & 3 of the call {v >> 2, it, 1} and is 1 below
+// its threshold (0xFFFFFFFF: always); a variable that occurs twice is drawn twice to the same value.
+template <bool BIASED>
 __device__ __forceinline__ void small_join(uint32_t* s_claim, uint32_t* s_A, uint32_t* s_ctl, const uint16_t* s_lits,
                                            uint32_t j0, uint32_t j1, uint32_t it_lo, uint32_t it_hi, uint32_t k0,
-                                           uint32_t k1) {
+                                           uint32_t k1, const SmallThr& T) {
     for (uint32_t j = j0; j < j1; ++j) {
         const uint32_t v = s_lits[j] >> 1, bit = 1u << (v & 31u);
         s_claim[v] = 0;
-        if (philox_x(v >> 5, it_lo, 0u, it_hi, k0, k1) & bit) atomicOr(&s_A[v >> 5], bit);
+        bool one;
+        if (BIASED && T.on) {
+            const uint4 q = philox_4(v >> 2, it_lo, 1u, it_hi, k0, k1);
+            const uint32_t e = v & 3u, x = e == 0 ? q.x : e == 1 ? q.y : e == 2 ? q.z : q.w;
+            const uint32_t t = T.in_lds ? T.lds[v] : T.glb[v];
+            one = (x < t) | (t == 0xFFFFFFFFu);
+        } else {
+            one = (philox_x(v >> 5, it_lo, 0u, it_hi, k0, k1) & bit) != 0;
+        }
+        if (one) atomicOr(&s_A[v >> 5], bit);
         else atomicAnd(&s_A[v >> 5], ~bit);
     }
     atomicAdd(&s_ctl[2], 1u);
     atomicAdd(&s_ctl[3], j1 - j0);
 }
 
-__global__ void __launch_bounds__(1024) k_small(const SmallItem* __restrict__ items, SmallState* __restrict__ states,
+// The kernel's body.  BIASED = false is the kernel of a batch without thresholds (g_thr and thr_lds
+// unused); BIASED = true serves a batch with at least one biased item: thr_lds is the byte offset of
+// the LDS thresholds, 0 when the batch reads them from g_thr (item i's at 32 * a_at, zero-padded).
+template <bool BIASED>
+__device__ __forceinline__ void small_body(const SmallItem* __restrict__ items, SmallState* __restrict__ states,
                                                 const uint16_t* __restrict__ g_lits,
                                                 const uint16_t* __restrict__ g_offs, uint32_t* __restrict__ g_A,
-                                                const SmallLds L, const uint32_t slice,
-                                                const uint32_t serial_max) {
+                                                const SmallLds& L, const uint32_t slice,
+                                                const uint32_t serial_max, const uint32_t* __restrict__ g_thr,
+                                                const uint32_t thr_lds) {
     extern __shared__ __align__(16) unsigned char smem[];
     const SmallItem it = items[blockIdx.x];
     SmallState st = states[blockIdx.x];
@@ -79,8 +107,15 @@ __global__ void __launch_bounds__(1024) k_small(const SmallItem* __restrict__ it
         for (uint32_t i = tid; i < (m + 1u + 7u) / 8u; i += nt) dst[i] = src[i];
         for (uint32_t w = tid; w < it.n_words; w += nt) s_A[w] = g_A[it.a_at + w];
         if (tid < 8) s_ctl[tid] = 0;
+        if (BIASED && it.pad && thr_lds) {  // (32 * n_words entries in the pool: whole 16-byte vectors)
+            src = (const uint4*)(g_thr + 32ull * it.a_at);
+            dst = (uint4*)(smem + thr_lds);
+            for (uint32_t i = tid; i < (it.n_vars + 3u) / 4u; i += nt) dst[i] = src[i];
+        }
     }
     __syncthreads();
+    const SmallThr T{(const uint32_t*)(smem + thr_lds), BIASED ? g_thr + 32ull * it.a_at : nullptr,
+                     BIASED && it.pad != 0, thr_lds != 0};
 
     const uint32_t k0 = (uint32_t)it.seed, k1 = (uint32_t)(it.seed >> 32);
     uint64_t n_iter = st.n_iter;
@@ -158,7 +193,7 @@ __global__ void __launch_bounds__(1024) k_small(const SmallItem* __restrict__ it
                     if (lane == i) {
                         bool open = true;
                         for (uint32_t j = j0; j < j1; ++j) open &= *(volatile uint32_t*)&s_claim[s_lits[j] >> 1] != 0u;
-                        if (open) small_join(s_claim, s_A, s_ctl, s_lits, j0, j1, it_lo, it_hi, k0, k1);
+                        if (open) small_join<BIASED>(s_claim, s_A, s_ctl, s_lits, j0, j1, it_lo, it_hi, k0, k1, T);
                     }
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // lane i's cover marks before lane i + 1 looks
                 }
@@ -176,7 +211,7 @@ __global__ void __launch_bounds__(1024) k_small(const SmallItem* __restrict__ it
                 bool win = true;
                 for (uint32_t j = j0; j < j1; ++j) win &= s_claim[s_lits[j] >> 1] == (ep | c);
                 if (!win) continue;
-                small_join(s_claim, s_A, s_ctl, s_lits, j0, j1, it_lo, it_hi, k0, k1);
+                small_join<BIASED>(s_claim, s_A, s_ctl, s_lits, j0, j1, it_lo, it_hi, k0, k1, T);
                 lc[i] = (uint16_t)(c | SM_JOINED);
             }
             __syncthreads();
@@ -220,6 +255,24 @@ __global__ void __launch_bounds__(1024) k_small(const SmallItem* __restrict__ it
     }
 }
 
+__global__ void __launch_bounds__(1024) k_small(const SmallItem* __restrict__ items, SmallState* __restrict__ states,
+                                                const uint16_t* __restrict__ g_lits,
+                                                const uint16_t* __restrict__ g_offs, uint32_t* __restrict__ g_A,
+                                                const SmallLds L, const uint32_t slice,
+                                                const uint32_t serial_max) {
+    small_body<false>(items, states, g_lits, g_offs, g_A, L, slice, serial_max, nullptr, 0u);
+}
+
+__global__ void __launch_bounds__(1024) k_small_biased(const SmallItem* __restrict__ items,
+                                                       SmallState* __restrict__ states,
+                                                       const uint16_t* __restrict__ g_lits,
+                                                       const uint16_t* __restrict__ g_offs, uint32_t* __restrict__ g_A,
+                                                       const SmallLds L, const uint32_t slice,
+                                                       const uint32_t serial_max, const uint32_t* __restrict__ g_thr,
+                                                       const uint32_t thr_lds) {
+    small_body<true>(items, states, g_lits, g_offs, g_A, L, slice, serial_max, g_thr, thr_lds);
+}
+
 __global__ void k_small_init(const SmallItem* __restrict__ items, uint32_t* __restrict__ g_A) {
     const SmallItem it = items[blockIdx.x];
     for (uint32_t w = threadIdx.x; w < it.n_words; w += blockDim.x) {
@@ -248,7 +301,11 @@ __global__ void k_small_limits(SmallState* __restrict__ states, uint32_t n_items
 hipError_t small_prepare() {
     // (the attribute is the kernel's, not the batch's: the footprint of an item at the limits)
     const SmallLds top = small_lds_layout(ALLL_BATCH_MAX_VARS, ALLL_BATCH_MAX_CLAUSES, ALLL_BATCH_MAX_LITERALS);
-    return hipFuncSetAttribute((const void*)k_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)top.bytes);
+    hipError_t e = hipFuncSetAttribute((const void*)k_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)top.bytes);
+    if (e != hipSuccess) return e;
+    // (with LDS thresholds a layout goes up to the budget; beyond it the batch reads them from global memory)
+    return hipFuncSetAttribute((const void*)k_small_biased, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)SMALL_LDS_BUDGET);
 }
 
 hipError_t launch_small_init(const SmallBatch& b, hipStream_t s) {
@@ -263,6 +320,12 @@ hipError_t launch_small_limits(const SmallBatch& b, bool solve, uint64_t value, 
 }
 
 hipError_t launch_small_slice(const SmallBatch& b, uint32_t slice, hipStream_t s) {
+    if (b.biased) {  // at least one item has thresholds
+        const uint32_t bytes = b.thr_lds ? b.lds_thr_bytes : b.lds.bytes;
+        hipLaunchKernelGGL(k_small_biased, dim3(b.n_items), dim3(b.threads), bytes, s, b.items, b.states, b.lits,
+                           b.offs, b.A, b.lds, slice, b.serial_max, b.thr, b.thr_lds);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_small, dim3(b.n_items), dim3(b.threads), b.lds.bytes, s, b.items, b.states, b.lits, b.offs,
                        b.A, b.lds, slice, b.serial_max);
     return hipGetLastError();

@@ -116,6 +116,20 @@ def biased_initial_assignment(seed: int, n_vars: int, thr) -> np.ndarray:
     return out[:n_vars]
 
 
+def pinned_conflict(n_vars: int, offsets, literals, thr) -> Optional[int]:
+    """alll_pinned_conflict: the first clause whose literals are all pinned false by thresholds thr
+    (an empty clause counts), or None when every clause can still be met (host-only)."""
+    offs = np.ascontiguousarray(offsets, np.uint64)
+    lits = np.ascontiguousarray(literals, np.uint32)
+    thr = np.ascontiguousarray(thr, np.uint32)
+    m = max(0, offs.size - 1)
+    prob = N.Problem(int(n_vars), 0, m, _p(offs, _u64p), _p(lits, _u32p))
+    c = ctypes.c_uint64()
+    N.check(N.lib().alll_pinned_conflict(ctypes.byref(prob), _p(thr, _u32p), thr.size, ctypes.byref(c)),
+            "pinned_conflict")
+    return None if c.value == m else int(c.value)
+
+
 # ----------------------------------------------------------------------------- Solver
 class Solver:
     """Owns one device solver context (alll_ctx).  probabilities: P(x_v = 1) per variable (0 and 1
@@ -435,6 +449,20 @@ class BatchSolver:
         """Iterations per kernel launch (0: the default)."""
         N.check(self._L.alll_batch_set_slice(self._b, n), "alll_batch_set_slice")
 
+    def set_probabilities(self, i: int, p):
+        """Solver.set_probabilities for item i: it then computes what a Solver with seeds[i] and the
+        same probabilities computes.  Items that are one instance under different pinned variables
+        and solve(first_solved=True) make a cube portfolio (solve_cubes)."""
+        self.set_thresholds(i, None if p is None else var_thresholds(p))
+
+    def set_thresholds(self, i: int, thr):
+        """alll_batch_set_var_thresholds: the item's n_vars uint32 thresholds, or None."""
+        if thr is None:
+            N.check(self._L.alll_batch_set_var_thresholds(self._b, i, None, 0), "batch set_var_thresholds")
+            return
+        thr = np.ascontiguousarray(thr, np.uint32)
+        N.check(self._L.alll_batch_set_var_thresholds(self._b, i, _p(thr, _u32p), thr.size), "batch set_var_thresholds")
+
 
 class GroupSolver:
     """Owns one block-diagonal group (alll_group): item i is problems[i] = (n_vars, offsets,
@@ -553,6 +581,53 @@ def solve_portfolio(n_vars: int, offsets, literals, seeds, max_iters: int = 0):
             return None, None, None
         best = min(solved, key=lambda i: (res[i]["n_iterations"], i))
         return seeds[best], res[best], b.assignment_words(best)
+
+
+def cube_thresholds(n_vars: int, cube) -> np.ndarray:
+    """The thresholds of a cube, a sequence of encoded literals assumed true: 2v pins x_v = 1, 2v+1
+    pins x_v = 0, every other variable is a fair coin.  ValueError for a variable >= n_vars and for
+    a cube that names both polarities of one."""
+    thr = np.full(n_vars, 1 << 31, np.uint32)
+    seen = {}
+    for l in cube:
+        l = int(l)
+        v = l >> 1
+        if l < 0 or v >= n_vars:
+            raise ValueError(f"cube literal {l} names variable {v} >= n_vars {n_vars}")
+        if seen.setdefault(v, l) != l:
+            raise ValueError(f"cube names both polarities of variable {v}")
+        thr[v] = 0 if l & 1 else 0xFFFFFFFF
+    return thr
+
+
+def solve_cubes(n_vars: int, offsets, literals, cubes, seeds=None, max_iters: int = 0):
+    """A cube portfolio: one instance under every cube's pins (cube_thresholds) at once, the first
+    cube solved wins.  seeds: one per cube, default 1 .. len(cubes).  Cubes that pin every literal
+    of some clause false (pinned_conflict) are dropped on the host; the others run in a BatchSolver
+    when the instance fits one, else in a GroupSolver.  Returns (cube index, stats,
+    assignment_words) of the solved cube with the fewest iterations (on a tie the lowest index), or
+    (None, None, None) when no cube is left or max_iters capped every one."""
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    literals = np.ascontiguousarray(literals, np.uint32)
+    cubes = list(cubes)
+    seeds = list(range(1, len(cubes) + 1)) if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != len(cubes):
+        raise ValueError(f"{len(cubes)} cubes, {len(seeds)} seeds")
+    thrs = [cube_thresholds(n_vars, c) for c in cubes]
+    live = [i for i, t in enumerate(thrs) if pinned_conflict(n_vars, offsets, literals, t) is None]
+    if not live:
+        return None, None, None
+    fits = batch_fits(n_vars, max(0, offsets.size - 1), literals.size)
+    cls = BatchSolver if fits else GroupSolver
+    with cls([(n_vars, offsets, literals)] * len(live), [seeds[i] for i in live], max_iters=max_iters) as b:
+        for k, i in enumerate(live):
+            b.set_thresholds(k, thrs[i])
+        res = b.solve(first_solved=True)
+        solved = [k for k, r in enumerate(res) if r["solved"]]
+        if not solved:
+            return None, None, None
+        best = min(solved, key=lambda k: (res[k]["n_iterations"], k))
+        return live[best], res[best], b.assignment_words(best)
 
 
 def shard_plan(n_clauses: int, world: int, rank: int):

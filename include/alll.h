@@ -312,6 +312,19 @@ int alll_batch_get_assignment_words(alll_batch* b, uint64_t item, uint32_t* out,
 int alll_batch_set_assignment_words(alll_batch* b, uint64_t item, const uint32_t* in, uint64_t n_words);
 /* Iterations per kernel launch, 1 .. ALLL_BATCH_MAX_SLICE; 0 = the measured default. */
 int alll_batch_set_slice(alll_batch* b, uint64_t iters_per_launch);
+/* alll_set_var_thresholds for one item (n == the item's n_vars; the key is seeds[item]): item i then
+ * behaves exactly as a context created from probs[i] with {seed = seeds[i], n_threads = 1, flags = 0,
+ * max_iters} and given the same thresholds (the biased fill u0, the biased draw u(v, it) with counter
+ * word 2 = 1, the same statistics); items without thresholds keep the unbiased stream bit for bit.
+ * Thresholds belong to the item, not to the stored problem: items that share one copy of the clauses
+ * may each have their own.  Allowed while that item's n_iterations == 0, else ALLL_ERR_INVALID_ARG,
+ * as n != the item's n_vars, a null batch or item >= n_items; a refused call changes nothing.  The
+ * call copies the thresholds (no caller pointer is kept) and rewrites that item's assignment words
+ * only; thr == NULL (n ignored) restores the unbiased fill and stream of that item.
+ * alll_batch_set_assignment_words afterwards is not checked against the pins.  With
+ * ALLL_BATCH_FIRST_SOLVED, items that are one instance under different pinned variables make a cube
+ * portfolio (alll_pinned_conflict drops the cubes that cannot be met). */
+int alll_batch_set_var_thresholds(alll_batch* b, uint64_t item, const uint32_t* thr, uint64_t n);
 
 /* ---- block-diagonal groups: many instances of any size at once -------
  * The items are laid side by side as one instance with disjoint variable and clause ranges, and
@@ -422,6 +435,14 @@ int alll_var_threshold(double p, uint32_t* thr);
 /* The biased initial fill (alll_set_var_thresholds, u0) for `seed` and n_vars thresholds, as
  * n_vars bytes of 0/1. */
 int alll_biased_initial_assignment(uint64_t seed, uint32_t n_vars, const uint32_t* thr, uint8_t* out);
+/* Pins that cannot be met: *clause = the index of the first clause whose literals are all pinned
+ * false by thr (n == n_vars entries): a literal 2v when thr[v] == 0, a literal 2v+1 when thr[v] ==
+ * 0xFFFFFFFF; an empty clause counts as one.  *clause = n_clauses when there is none.  The loop
+ * does not detect such a clause (it runs to max_iters): a cube portfolio drops its dead cubes with
+ * this before they occupy a workgroup.  Validates as alll_create: a null pointer or n != n_vars:
+ * ALLL_ERR_INVALID_ARG; offsets that do not start at 0 or decrease: ALLL_ERR_BAD_INPUT; a literal
+ * of a variable >= n_vars: ALLL_ERR_LITERAL_RANGE (*clause is then left alone). */
+int alll_pinned_conflict(const alll_problem* prob, const uint32_t* thr, uint64_t n, uint64_t* clause);
 
 /* The reference's own initial assignment (VariablesArray.h:23-34) in the reference-RNG mode
  * (ALLL_FLAG_REFERENCE_RNG): `rd_state` is the random_device stand-in's state

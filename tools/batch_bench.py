@@ -10,7 +10,15 @@ profiles/batch/summary.txt:
   (s) the slice rule's input: per-iteration time of one launch of items at the limits that never
       solve (2048 variables, 8192 clauses: ratio 4), 64 and 256 items, several slice lengths;
   (g) the LFMIS choice: the workloads of (b) and (a) with the one-wave serial greedy taking the
-      violated sets of at most 0 (never), 4, 16 and 64 clauses (ALLL_BATCH_SERIAL_MAX).
+      violated sets of at most 0 (never), 4, 16 and 64 clauses (ALLL_BATCH_SERIAL_MAX);
+  (u) the batch leg of (a) alone, best of 5, with a digest of every item's result; with --ab-lib
+      OTHER.so it runs alternately on this build and on OTHER (ALLL_LIB_AB), three pairs in both
+      orders: the unbiased batch of two builds side by side;
+  (t) the cost of per-variable thresholds: the workload of (a), and 64 items of
+      2048 / 8192 for 256 iterations, unbiased, with every threshold at 2^31 LDS-resident, and
+      with the thresholds read from global memory (ALLL_BATCH_THR_GLOBAL=1), in one process;
+  (q) a cube portfolio: the 256 cubes of variables 0..7 of the 200 / 520 instance of (b), time
+      from create to the first answer in a BatchSolver and in a GroupSolver.
 
 Every leg runs in a child process of its own under a time limit; after a leg that fails, is
 killed or times out, nothing more is started.  Times are host wall clock around calls that end
@@ -26,7 +34,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LEG_TIMEOUT = {"a": 240, "b": 60, "c": 60, "s": 120, "g": 60}
+LEG_TIMEOUT = {"a": 240, "b": 60, "c": 60, "s": 120, "g": 60, "u": 60, "t": 120, "q": 120}
 SERIAL_MAX = (0, 4, 16, 64)
 
 
@@ -150,6 +158,90 @@ def leg_g():
     return out
 
 
+def _digest(res, words):
+    import hashlib
+
+    h = hashlib.sha256()
+    keys = ("n_iterations", "n_resamples", "sum_mis_size", "n_violated", "solved")
+    for r, w in zip(res, words):
+        h.update(repr([r[k] for k in keys]).encode() + w.tobytes())
+    return h.hexdigest()[:16]
+
+
+def _timed_batch(problems, seeds, thr, reps, cap=0, run=0):
+    """Best-of-reps input: solve (or run(run)) of one batch, every item under thresholds thr (None: unbiased)."""
+    from alllsatisfiabilitysolver_amd import BatchSolver
+
+    t, iters, dig = [], 0, None
+    for _ in range(reps + 1):  # (the first one warms up)
+        with BatchSolver(problems, seeds, max_iters=cap) as b:
+            if thr is not None:
+                for i in range(len(seeds)):
+                    b.set_thresholds(i, thr)
+            t0 = time.perf_counter()
+            res = b.run(run) if run else b.solve()
+            t.append(time.perf_counter() - t0)
+            iters = sum(r["n_iterations"] for r in res)
+            dig = _digest(res, [b.assignment_words(i) for i in range(len(seeds))])
+    return {"iterations": iters, "digest": dig, "ms": [x * 1e3 for x in t[1:]]}
+
+
+def leg_u():
+    from alllsatisfiabilitysolver_amd import generate_ksat
+
+    n, m, cap, items = 200, 800, 2000, 256
+    offs, lits = generate_ksat(1, n, m, 3)
+    out = _timed_batch([(n, offs, lits)] * items, list(range(1, items + 1)), None, 5, cap=cap)
+    return dict(out, leg="u", lib=os.environ.get("ALLL_LIB_AB", "this build"))
+
+
+def leg_t():
+    import numpy as np
+    from alllsatisfiabilitysolver_amd import generate_ksat
+
+    out = {"leg": "t", "rows": []}
+    for name, n, m, items, cap, run in (("200/800", 200, 800, 256, 2000, 0), ("2048/8192", 2048, 8192, 64, 0, 256)):
+        offs, lits = generate_ksat(1, n, m, 3)
+        problems, seeds = [(n, offs, lits)] * items, list(range(1, items + 1))
+        half = np.full(n, 1 << 31, np.uint32)
+        for mode, thr, env in (("unbiased", None, None), ("thresholds in LDS", half, None),
+                               ("thresholds in global memory", half, "1"), ("unbiased again", None, None)):
+            os.environ.pop("ALLL_BATCH_THR_GLOBAL", None)
+            if env:
+                os.environ["ALLL_BATCH_THR_GLOBAL"] = env  # (read at create)
+            out["rows"].append(dict(_timed_batch(problems, seeds, thr, 5, cap=cap, run=run), size=name, items=items,
+                                    mode=mode))
+    os.environ.pop("ALLL_BATCH_THR_GLOBAL", None)
+    return out
+
+
+def leg_q():
+    from alllsatisfiabilitysolver_amd import (BatchSolver, GroupSolver, cube_thresholds, generate_ksat,
+                                              pinned_conflict)
+
+    n, m, cap = 200, 520, 100000
+    offs, lits = generate_ksat(1, n, m, 3)
+    cubes = [[2 * v + 1 - ((i >> v) & 1) for v in range(8)] for i in range(256)]
+    out = {"leg": "q", "n_vars": n, "n_clauses": m, "cubes": len(cubes)}
+    for name, cls in (("batch", BatchSolver), ("group", GroupSolver)):
+        t = []
+        for rep in range(4):  # (the first one warms up)
+            t0 = time.perf_counter()
+            thrs = [cube_thresholds(n, c) for c in cubes]
+            live = [i for i, x in enumerate(thrs) if pinned_conflict(n, offs, lits, x) is None]
+            with cls([(n, offs, lits)] * len(live), [i + 1 for i in live], max_iters=cap) as b:
+                for k, i in enumerate(live):
+                    b.set_thresholds(k, thrs[i])
+                res = b.solve(first_solved=True)
+                solved = [k for k, r in enumerate(res) if r["solved"]]
+                best = min(solved, key=lambda k: (res[k]["n_iterations"], k))
+                b.assignment_words(best)
+            t.append(time.perf_counter() - t0)
+        out[name] = {"live": len(live), "winner": live[best], "winner_iterations": res[best]["n_iterations"],
+                     "ms": [x * 1e3 for x in t[1:]]}
+    return out
+
+
 def summary(r):
     out = ["Batch path on one MI355X (tools/batch_bench.py); host wall clock around synchronising calls.", ""]
     a, b, c, s = (r.get(k) for k in "abcs")
@@ -199,12 +291,37 @@ def summary(r):
                 cells.append(f"{min(ms):7.2f}  ({' '.join(f'{v:.2f}' for v in ms)})")
             out.append(f"    {x['serial_max']:6d}   {cells[0]:48s} {cells[1]}")
         out.append("")
+    u = [r[k] for k in sorted(r) if k.startswith("u")]
+    if u:
+        out += ["(u) the batch of (a) alone on two builds, alternately (solve ms, best of 5; all 5; digest of the results):"]
+        for x in u:
+            out.append(f"    {os.path.basename(x['lib']):24s} {min(x['ms']):8.3f}  ({' '.join(f'{v:.3f}' for v in x['ms'])})  "
+                       f"{x['iterations']} iterations  {x['digest']}")
+        out.append("")
+    t = r.get("t")
+    if t:
+        out += ["(t) per-variable thresholds, every item at thr = 2^31 (ms, best of 5; all 5):"]
+        for x in t["rows"]:
+            out.append(f"    {x['size']:10s} {x['items']:4d} items  {x['mode']:28s} {min(x['ms']):9.3f}  "
+                       f"({' '.join(f'{v:.3f}' for v in x['ms'])})  {x['iterations']} iterations  {x['digest']}")
+        out.append("")
+    q = r.get("q")
+    if q:
+        out += [f"(q) cube portfolio: {q['cubes']} cubes of variables 0..7, {q['n_vars']} variables / {q['n_clauses']} clauses, "
+                "create to first answer (ms, best of 3; all 3):"]
+        for name in ("batch", "group"):
+            x = q[name]
+            out.append(f"    {name:6s} {min(x['ms']):9.2f}  ({' '.join(f'{v:.2f}' for v in x['ms'])})  {x['live']} live cubes, "
+                       f"winner cube {x['winner']} after {x['winner_iterations']} iterations")
+        out.append("")
     return "\n".join(out)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=["a", "b", "c", "s", "g"], help="run one leg in this process, print its JSON line")
+    ap.add_argument("--leg", choices=["a", "b", "c", "s", "g", "u", "t", "q"],
+                    help="run one leg in this process, print its JSON line")
+    ap.add_argument("--ab-lib", help="leg u: another build's liballl.so to alternate with (three pairs, both orders)")
     ap.add_argument("--legs", default="abcsg")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch", "summary.txt"))
     args = ap.parse_args()
@@ -213,11 +330,17 @@ def main():
 
         if device_count() < 1:
             raise SystemExit("batch_bench: no HIP device visible (no fallback)")
-        print(json.dumps({"a": leg_a, "b": leg_b, "c": leg_c, "s": leg_s, "g": leg_g}[args.leg]()), flush=True)
+        legs = {"a": leg_a, "b": leg_b, "c": leg_c, "s": leg_s, "g": leg_g, "u": leg_u, "t": leg_t, "q": leg_q}
+        print(json.dumps(legs[args.leg]()), flush=True)
         return 0
     results = {}
     env = {k: v for k, v in os.environ.items() if k != "ALLL_BATCH_SERIAL_MAX"}  # (the library's default)
-    runs = [(leg, leg, env) for leg in args.legs if leg != "g"]
+    env.pop("ALLL_LIB_AB", None)
+    runs = [(leg, leg, env) for leg in args.legs if leg not in "gu"]
+    if "u" in args.legs:
+        other = dict(env, ALLL_LIB_AB=os.path.abspath(args.ab_lib)) if args.ab_lib else None
+        order = [other, env, env, other, other, env] if other else [env]
+        runs += [("u", f"u{i}", e) for i, e in enumerate(order)]
     if "g" in args.legs:
         runs += [("g", f"g{i}", dict(env, ALLL_BATCH_SERIAL_MAX=str(sm))) for i, sm in enumerate(SERIAL_MAX)]
     for leg, key, e in runs:
