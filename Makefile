@@ -18,7 +18,7 @@ GROUP_H := $(SRC)/alll_group.h $(SRC)/alll_group_dev.h
 
 all: $(LIB)
 
-$(SRC)/alll_kernels.o: $(SRC)/alll_kernels.hip $(SRC)/alll_internal.h $(SRC)/alll_philox.h $(GROUP_H)
+$(SRC)/alll_kernels.o: $(SRC)/alll_kernels.hip $(SRC)/alll_internal.h $(SRC)/alll_draws.h $(GROUP_H)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 $(SRC)/alll_stream.o: $(SRC)/alll_stream.hip $(SRC)/alll_internal.h
@@ -27,32 +27,32 @@ $(SRC)/alll_stream.o: $(SRC)/alll_stream.hip $(SRC)/alll_internal.h
 $(SRC)/alll_refrng.o: $(SRC)/alll_refrng.hip $(SRC)/alll_internal.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(SRC)/alll_runtime.o: $(SRC)/alll_runtime.cpp $(SRC)/alll_layout.h $(SRC)/alll_internal.h $(GROUP_H) include/alll.h
+$(SRC)/alll_runtime.o: $(SRC)/alll_runtime.cpp $(SRC)/alll_layout.h $(SRC)/alll_internal.h $(SRC)/alll_rt_util.h $(GROUP_H) include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 $(SRC)/alll_layout.o: $(SRC)/alll_layout.cpp $(SRC)/alll_layout.h $(SRC)/alll_internal.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(SRC)/alll_host.o: $(SRC)/alll_host.cpp include/alll.h
+$(SRC)/alll_host.o: $(SRC)/alll_host.cpp $(SRC)/alll_draws.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 # batches of LDS-resident instances: kernel, host-only planner, device set-up
 # (SMALL_REMARKS=-Rpass-analysis=kernel-resource-usage prints the registers, scratch and LDS of both
 # instantiations of the batch kernel: DESIGN.md §4.6)
-$(SRC)/alll_small.o: $(SRC)/alll_small.hip $(SRC)/alll_small.h $(SRC)/alll_batch.h $(SRC)/alll_philox.h include/alll.h
+$(SRC)/alll_small.o: $(SRC)/alll_small.hip $(SRC)/alll_small.h $(SRC)/alll_batch.h $(SRC)/alll_draws.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) $(SMALL_REMARKS) -c -o $@ $<
 
 $(SRC)/alll_batch.o: $(SRC)/alll_batch.cpp $(SRC)/alll_batch.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(SRC)/alll_batch_runtime.o: $(SRC)/alll_batch_runtime.cpp $(SRC)/alll_small.h $(SRC)/alll_batch.h include/alll.h
+$(SRC)/alll_batch_runtime.o: $(SRC)/alll_batch_runtime.cpp $(SRC)/alll_small.h $(SRC)/alll_batch.h $(SRC)/alll_rt_util.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 # block-diagonal groups: host-only planner, device set-up (the kernels are in alll_kernels.hip)
 $(SRC)/alll_group.o: $(SRC)/alll_group.cpp $(SRC)/alll_group.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(SRC)/alll_group_runtime.o: $(SRC)/alll_group_runtime.cpp $(GROUP_H) $(SRC)/alll_internal.h include/alll.h
+$(SRC)/alll_group_runtime.o: $(SRC)/alll_group_runtime.cpp $(GROUP_H) $(SRC)/alll_internal.h $(SRC)/alll_rt_util.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 # (linked to a temporary name and renamed: a tree snapshot taken meanwhile sees the old or the new library)

@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,31 +13,12 @@
 
 #include "alll.h"
 #include "alll_batch.h"
+#include "alll_rt_util.h"
 #include "alll_small.h"
 
 using namespace alll;
 
-extern "C" void alll_internal_set_error(const char* msg);
-
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    alll_internal_set_error(buf);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess)                                                            \
-            return fail(ALLL_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                        __FILE__, __LINE__);                                             \
-    } while (0)
 
 // Iterations per launch.  Measured on the MI355X (profiles/batch/summary.txt):
 // items of 8192 clauses that never solve take 17.5 - 18.6 us per iteration (64 and 256 items, one

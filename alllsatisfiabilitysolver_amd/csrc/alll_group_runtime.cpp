@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -15,32 +14,9 @@
 #include "alll.h"
 #include "alll_group.h"
 #include "alll_group_dev.h"
+#include "alll_rt_util.h"
 
 using namespace alll;
-
-extern "C" void alll_internal_set_error(const char* msg);
-
-namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    alll_internal_set_error(buf);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess)                                                            \
-            return fail(ALLL_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                        __FILE__, __LINE__);                                             \
-    } while (0)
-
-}  // namespace
 
 struct alll_group {
     alll_ctx* ctx = nullptr;

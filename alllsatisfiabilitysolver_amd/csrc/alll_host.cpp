@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "alll.h"
+#include "alll_draws.h"
 
 extern "C" void alll_internal_set_error(const char* msg);
 
@@ -403,28 +404,6 @@ void gen_range(uint64_t seed, uint32_t n, uint32_t k, int kind, uint64_t cb, uin
     }
 }
 
-// Philox4x32-10, all four output words in Random123 order
-void philox_4_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0;
-        c1 = (uint32_t)p1;
-        c2 = n2;
-        c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-uint32_t philox_x_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-    uint32_t o[4];
-    philox_4_host(c0, c1, c2, c3, k0, k1, o);
-    return o[0];
-}
-
 // The reference's VariablesArray fill (VariablesArray.h:23-34) in the reference-RNG mode: the
 // same stream as k_rrng_init (alll_refrng.hip) -- the random_device stand-in's
 // next value seeds minstd_rand0, libstdc++'s uniform_int_distribution<unsigned long long> upscales
@@ -483,7 +462,7 @@ int alll_reference_initial_assignment(uint64_t rd_state, uint32_t n_vars, uint8_
 int alll_initial_assignment(uint64_t seed, uint32_t n_vars, uint8_t* out) {
     if (!out && n_vars) return ALLL_ERR_INVALID_ARG;
     for (uint32_t w = 0; w < (n_vars + 31) / 32; ++w) {
-        const uint32_t x = philox_x_host(w, 0u, 0xFFFFFFFFu, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+        const uint32_t x = alll::fill_word((uint32_t)seed, (uint32_t)(seed >> 32), w);
         for (uint32_t b = 0; b < 32 && 32 * w + b < n_vars; ++b) out[32 * w + b] = (x >> b) & 1u;
     }
     return ALLL_OK;
@@ -506,10 +485,10 @@ int alll_var_threshold(double p, uint32_t* thr) {
 
 int alll_biased_initial_assignment(uint64_t seed, uint32_t n_vars, const uint32_t* thr, uint8_t* out) {
     if ((!out || !thr) && n_vars) return ALLL_ERR_INVALID_ARG;
-    uint32_t u[4] = {0, 0, 0, 0};
+    alll::Word4 u{0, 0, 0, 0};
     for (uint32_t v = 0; v < n_vars; ++v) {
-        if ((v & 3u) == 0) philox_4_host(v >> 2, 0u, 0xFFFFFFFEu, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), u);
-        out[v] = thr[v] == 0xFFFFFFFFu ? 1 : (uint8_t)(u[v & 3u] < thr[v]);
+        if ((v & 3u) == 0) u = alll::biased_fill_call((uint32_t)seed, (uint32_t)(seed >> 32), v >> 2);
+        out[v] = (uint8_t)alll::biased_bit(alll::call_word(u, v & 3u), thr[v]);
     }
     return ALLL_OK;
 }

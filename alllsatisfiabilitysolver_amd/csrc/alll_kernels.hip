@@ -22,7 +22,7 @@
 
 #include "alll_group_dev.h"
 #include "alll_internal.h"
-#include "alll_philox.h"
+#include "alll_draws.h"
 
 namespace alll {
 
@@ -38,8 +38,6 @@ namespace alll {
         case 8: { constexpr int K = 8; CALL; } break;  \
         default: { constexpr int K = 0; CALL; } break; \
     }
-
-// (philox_x, the Philox4x32-10 of the initial assignment and the resample: alll_philox.h)
 
 // The AoS literal copy used by the LFMIS / resample kernels carries a "hot variable" flag in
 // bit 31 (set by the host for the highest-degree variables of skewed instances).
@@ -172,48 +170,41 @@ __device__ __forceinline__ uint32_t ent_lit(const ClauseView& cv, const Ent<K>& 
 __device__ __forceinline__ uint32_t lit_var(uint32_t raw) { return (raw & LIT_MASK) >> 1; }
 
 // ------------------------------------------------------------------------------------
-// Initial assignment: word w = Philox(seed, {w, 0, 0xFFFFFFFF, 0}).x (VariablesArray.h:23-34).
+// Initial assignment (VariablesArray.h:23-34), one body for the three fill kernels: word w is the
+// fill word of its key and local index (alll_draws.h), the bits past the last variable cleared.
+//   k_init_assignment  the key is the seed, the local index w, the tail from n_vars
+//   k_group_init        every word keyed by the item that owns it: key, local index and
+//                      tail mask are the word's GroupWord, one 16-byte load
+//   k_init_biased       k_init_assignment with the biased fill of the word's 32
+//                      thresholds; thr holds 32 * n_words entries, zeros past n_vars.  A group fills
+//                      one item's words with it: A, thr and the variables are the item's.
+template <bool GROUP, bool BIASED>
+__device__ __forceinline__ void fill_body(uint32_t* A, uint32_t n_words, uint32_t n_vars, const uint32_t* thr,
+                                          uint64_t seed, const GroupWord* words) {
+    static_assert(!(GROUP && BIASED), "a group's biased items are filled one by one");
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    if constexpr (GROUP) {
+        const uint4 g = reinterpret_cast<const uint4*>(words)[w];  // {seed lo, seed hi, local word, tail mask}
+        A[w] = fill_word(g.x, g.y, g.z) & g.w;
+    } else {
+        const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+        uint32_t x;
+        if constexpr (BIASED) x = biased_fill_word(k0, k1, w, reinterpret_cast<const Word4*>(thr) + 8ull * w);
+        else x = fill_word(k0, k1, w);
+        if (w == n_words - 1 && (n_vars & 31u)) x &= (1u << (n_vars & 31u)) - 1u;
+        A[w] = x;
+    }
+}
+
 __global__ void k_init_assignment(uint32_t* A, uint32_t n_words, uint32_t n_vars, uint64_t seed) {
-    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= n_words) return;
-    uint32_t x = philox_x(w, 0u, 0xFFFFFFFFu, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-    if (w == n_words - 1 && (n_vars & 31u)) x &= (1u << (n_vars & 31u)) - 1u;
-    A[w] = x;
+    fill_body<false, false>(A, n_words, n_vars, nullptr, seed, nullptr);
 }
-
-// Groups: the same fill with every word keyed by the item that owns it, word w of
-// item i = Philox(seeds[i], {w - word_base[i], 0, 0xFFFFFFFF, 0}).x, the bits above the item's
-// n_vars cleared in its last word (GroupWord::tail_mask).
 __global__ void k_group_init(uint32_t* A, uint32_t n_words, const GroupWord* words) {
-    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= n_words) return;
-    const uint4 g = reinterpret_cast<const uint4*>(words)[w];  // {seed lo, seed hi, local word, tail mask}
-    A[w] = philox_x(g.z, 0u, 0xFFFFFFFFu, 0u, g.x, g.y) & g.w;
+    fill_body<true, false>(A, n_words, 0u, nullptr, 0ull, words);
 }
-
-// Per-variable probabilities: variable v draws its own 32-bit word, element v & 3
-// of the Philox call with counter word 0 = v >> 2, and is 1 when the word lies below its threshold;
-// thr = 0 pins it to 0, thr = 0xFFFFFFFF to 1 (a word of 0xFFFFFFFF is below no threshold).
-// -> bit j = the draw of the call's variable j.
-__device__ __forceinline__ uint32_t biased_bits4(const uint4 u, const uint4 t) {
-    return (uint32_t)((u.x < t.x) | (t.x == 0xFFFFFFFFu)) | (uint32_t)((u.y < t.y) | (t.y == 0xFFFFFFFFu)) << 1 |
-           (uint32_t)((u.z < t.z) | (t.z == 0xFFFFFFFFu)) << 2 | (uint32_t)((u.w < t.w) | (t.w == 0xFFFFFFFFu)) << 3;
-}
-
-// The biased fill: word w from its 32 thresholds and the 8 calls {8w + j, 0, 0xFFFFFFFE, 0} (the
-// unbiased fill's counter word 2 is 0xFFFFFFFF: disjoint draws).  thr holds 32 * n_words entries,
-// zeros past n_vars.  A group fills one item's words with it: A, thr and the variables are the item's.
 __global__ void k_init_biased(uint32_t* A, uint32_t n_words, uint32_t n_vars, const uint32_t* thr, uint64_t seed) {
-    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= n_words) return;
-    const uint4* t4 = reinterpret_cast<const uint4*>(thr) + 8ull * w;
-    uint32_t x = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < 8; ++j)
-        x |= biased_bits4(philox_4(8u * w + j, 0u, 0xFFFFFFFEu, 0u, (uint32_t)seed, (uint32_t)(seed >> 32)), t4[j])
-             << (4 * j);
-    if (w == n_words - 1 && (n_vars & 31u)) x &= (1u << (n_vars & 31u)) - 1u;
-    A[w] = x;
+    fill_body<false, true>(A, n_words, n_vars, thr, seed, nullptr);
 }
 
 // Raw entry of the clause at evaluation position p with lits_t slots t[0..K-1], as the
@@ -2176,76 +2167,75 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tail(ClauseView cv, LoopBuffer
 // reads the 8-bit stamps of 16 variables (one 16-byte load), 2 lanes OR their halves into a
 // word's covered mask, and the first of them draws and writes the word: no per-clause atomics.
 // n_resamples counts every literal (SATInstance.h:363) in the joins.
-__device__ __forceinline__ uint32_t resample_word(uint64_t seed, uint64_t it, uint32_t w) {
-    return philox_x(w, (uint32_t)it, 0u, (uint32_t)(it >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-
-__global__ __launch_bounds__(256) void k_resample_vars(LoopBuffers b) {
-    const DevState* st = b.state;
-    const int lane = threadIdx.x & 63;
-    const bool lead = (lane & 1) == 0;
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // variables 16t .. 16t+15
-    const uint32_t w = (uint32_t)(t >> 1);
-    const bool live = w < b.n_words;  // (cover is padded to whole words with zeros)
-    // the stamps and the word are loaded with the loop state (one round trip)
-    uint32_t a = 0;
-    if (lead && live) a = b.A[w];
-    uint4 c = make_uint4(0u, 0u, 0u, 0u);
-    if (live) c = reinterpret_cast<const uint4*>(b.cover)[t];
-    const uint32_t active = st->active, stamp = st->stamp;
-    const uint64_t it = st->n_iter - 1;
-    spec_fence();
-    if (!active) return;
-    const uint32_t cs[4] = {c.x, c.y, c.z, c.w};
-    uint32_t cm = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) cm |= (uint32_t)(((cs[i >> 2] >> (8 * (i & 3))) & 0xFFu) == stamp) << i;
-    cm <<= 16 * (lane & 1);
-    cm |= __shfl_xor(cm, 1, 64);
-    if (lead && cm) b.A[w] = (a & ~cm) | (resample_word(b.seed, it, w) & cm);
-}
-
-// The 16 biased draws of a lane: its variables are the four calls q4 .. q4 + 3
-// (counter word 0; their variables' thresholds are t4[0..3], 64 contiguous bytes), resample round
-// `it`, counter word 2 = 1 (the unbiased resample's is 0: disjoint draws).  -> bit i = variable i.
-__device__ __forceinline__ uint32_t biased_draw16(const uint4* t4, uint32_t q4, uint64_t it, uint32_t k0, uint32_t k1) {
-    uint32_t x = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j)
-        x |= biased_bits4(philox_4(q4 + j, (uint32_t)it, 1u, (uint32_t)(it >> 32), k0, k1), t4[j]) << (4 * j);
-    return x;
-}
-
-// k_resample_vars with per-variable probabilities (LoopBuffers::thr): the cover-stamp scheme is the
-// same, but a variable's draw is its own, so a lane whose 16 stamps cover anything loads its 16
-// thresholds and draws its 16 bits itself; the one exchange carries the lane's covered mask in the
-// low half and its bits in the high half.  A lane that covers nothing loads and draws nothing.
-__global__ __launch_bounds__(256) void k_resample_biased(LoopBuffers b) {
+//
+// One body for the four resample kernels; what differs between them is decided at compile time.
+//   BIASED (per-variable probabilities, DESIGN.md §4.8: LoopBuffers::thr, padded like cover): a
+//          variable's draw is its own, so a lane whose 16 stamps cover anything loads its 16 thresholds
+//          and draws its 16 bits itself (biased_draw16); the one exchange carries the lane's covered
+//          mask in the low half and its bits in the high half.  A lane that covers nothing loads and
+//          draws nothing.
+//   GROUP  (DESIGN.md §4.7): the draw is keyed by the item that owns the word, variable v local to the
+//          item (items start at word boundaries, so v % 32 is the bit of the union's word too).  The
+//          word's key and local index (GroupWord) are loaded with the stamps: by the lane that draws
+//          the word, or with BIASED by both lanes, as both draw -- the calls of a word's half are
+//          8 * local word + 4 * half + 0..3 -- and bit w % 32 of wbias[w / 32] says whether word w's
+//          item has thresholds; a word of an unbiased item takes the one-call draw, bit for bit.
+template <bool GROUP, bool BIASED>
+__device__ __forceinline__ void resample_body(const LoopBuffers& b, const GroupWord* words, const uint32_t* wbias) {
     const DevState* st = b.state;
     const int lane = threadIdx.x & 63;
     const bool lead = (lane & 1) == 0;
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // variables 16t .. 16t+15
     const uint32_t w = (uint32_t)(t >> 1);
     const bool live = w < b.n_words;  // (cover and thr are padded to whole words with zeros)
-    uint32_t a = 0;
-    if (lead && live) a = b.A[w];
+    // The stamps, the word and its key are loaded with the loop state (one round trip).  key =
+    // {key lo, key hi, local word}: without a group the seed and the word itself.  (The two shapes of
+    // the loads below are those of the kernels this body replaces: their machine code is unchanged.)
+    uint4 key = GROUP ? make_uint4(0u, 0u, 0u, 0u) : make_uint4((uint32_t)b.seed, (uint32_t)(b.seed >> 32), w, 0u);
+    uint32_t a = 0, biased = GROUP ? 0u : 1u;
     uint4 c = make_uint4(0u, 0u, 0u, 0u);
-    if (live) c = reinterpret_cast<const uint4*>(b.cover)[t];
+    if constexpr (GROUP && BIASED) {
+        if (live) {
+            if (lead) a = b.A[w];
+            key = reinterpret_cast<const uint4*>(words)[w];
+            biased = (wbias[w >> 5] >> (w & 31u)) & 1u;
+            c = reinterpret_cast<const uint4*>(b.cover)[t];
+        }
+    } else {
+        if (lead && live) {
+            a = b.A[w];
+            if constexpr (GROUP) key = reinterpret_cast<const uint4*>(words)[w];
+        }
+        if (live) c = reinterpret_cast<const uint4*>(b.cover)[t];
+    }
     const uint32_t active = st->active, stamp = st->stamp;
     const uint64_t it = st->n_iter - 1;
     spec_fence();
     if (!active) return;
     const uint32_t cs[4] = {c.x, c.y, c.z, c.w};
-    uint32_t x = 0;
+    uint32_t x = 0;  // bit i: variable 16t + i is covered
 #pragma unroll
     for (int i = 0; i < 16; ++i) x |= (uint32_t)(((cs[i >> 2] >> (8 * (i & 3))) & 0xFFu) == stamp) << i;
-    if (x)
-        x |= biased_draw16(reinterpret_cast<const uint4*>(b.thr) + 4 * t, (uint32_t)(4 * t), it, (uint32_t)b.seed,
-                           (uint32_t)(b.seed >> 32)) << 16;
-    const uint32_t y = __shfl_xor(x, 1, 64);  // (the odd lane's half: variables 16 .. 31 of the word)
-    const uint32_t cm = (x & 0xFFFFu) | (y << 16);
-    if (lead && cm) b.A[w] = (a & ~cm) | (((x >> 16) | (y & 0xFFFF0000u)) & cm);
+    if constexpr (BIASED) {
+        if (x && biased) {
+            const uint32_t q4 = GROUP ? 8u * key.z + 4u * (uint32_t)(lane & 1) : (uint32_t)(4 * t);
+            x |= biased_draw16(key.x, key.y, it, q4, reinterpret_cast<const Word4*>(b.thr) + 4 * t) << 16;
+        }
+        const uint32_t y = __shfl_xor(x, 1, 64);  // (the odd lane's half: variables 16 .. 31 of the word)
+        const uint32_t cm = (x & 0xFFFFu) | (y << 16);
+        if (lead && cm) {
+            const uint32_t bits = biased ? (x >> 16) | (y & 0xFFFF0000u) : resample_word(key.x, key.y, it, key.z);
+            b.A[w] = (a & ~cm) | (bits & cm);
+        }
+    } else {
+        uint32_t cm = x << 16 * (lane & 1);
+        cm |= __shfl_xor(cm, 1, 64);
+        if (lead && cm) b.A[w] = (a & ~cm) | (resample_word(key.x, key.y, it, key.z) & cm);
+    }
 }
+
+__global__ __launch_bounds__(256) void k_resample_vars(LoopBuffers b) { resample_body<false, false>(b, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void k_resample_biased(LoopBuffers b) { resample_body<false, true>(b, nullptr, nullptr); }
 
 // ------------------------------------------------------------------------------------
 // Block-diagonal groups (alll_group_dev.h): the union of the items runs the loop
@@ -2367,79 +2357,14 @@ __device__ void group_finish(const LoopBuffers& b, const GroupDev& g) {
     if (threadIdx.x == 0) g.ctl->acc_iter = it;
 }
 
-// k_resample_vars with the draw keyed by the item that owns the word: variable v of item i takes
-// bit v % 32 of Philox(seeds[i], {v / 32, it_lo, 0, it_hi}).x, v local to the item (items start at
-// word boundaries, so v % 32 is the bit of the union's word too).  The word's key and local index
-// (GroupWord) are loaded with the stamps; the cover-stamp scheme is k_resample_vars's.
+// The group's resample kernels (resample_body): the keyed draw, and group_finish in the last workgroup.
 __global__ __launch_bounds__(256) void k_group_resample(LoopBuffers b, GroupDev g) {
     if (blockIdx.x == gridDim.x - 1) { group_finish(b, g); return; }
-    const DevState* st = b.state;
-    const int lane = threadIdx.x & 63;
-    const bool lead = (lane & 1) == 0;
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // variables 16t .. 16t+15
-    const uint32_t w = (uint32_t)(t >> 1);
-    const bool live = w < b.n_words;  // (cover is padded to whole words with zeros)
-    uint32_t a = 0;
-    uint4 key = make_uint4(0u, 0u, 0u, 0u);
-    if (lead && live) {
-        a = b.A[w];
-        key = reinterpret_cast<const uint4*>(g.words)[w];
-    }
-    uint4 c = make_uint4(0u, 0u, 0u, 0u);
-    if (live) c = reinterpret_cast<const uint4*>(b.cover)[t];
-    const uint32_t active = st->active, stamp = st->stamp;
-    const uint64_t it = st->n_iter - 1;
-    spec_fence();
-    if (!active) return;
-    const uint32_t cs[4] = {c.x, c.y, c.z, c.w};
-    uint32_t cm = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) cm |= (uint32_t)(((cs[i >> 2] >> (8 * (i & 3))) & 0xFFu) == stamp) << i;
-    cm <<= 16 * (lane & 1);
-    cm |= __shfl_xor(cm, 1, 64);
-    if (lead && cm)
-        b.A[w] = (a & ~cm) | (philox_x(key.z, (uint32_t)it, 0u, (uint32_t)(it >> 32), key.x, key.y) & cm);
+    resample_body<true, false>(b, g.words, nullptr);
 }
-
-// k_group_resample for a group with biased items: bit w % 32 of wbias[w / 32] says
-// whether word w's item has thresholds (b.thr, the union's; an item's variables are local, so the
-// calls of a word's half are 8 * local word + 4 * half + 0..3).  Both lanes of a word load its key,
-// as both draw; a word of an unbiased item takes k_group_resample's draw, bit for bit.
 __global__ __launch_bounds__(256) void k_group_resample_biased(LoopBuffers b, GroupDev g, const uint32_t* wbias) {
     if (blockIdx.x == gridDim.x - 1) { group_finish(b, g); return; }
-    const DevState* st = b.state;
-    const int lane = threadIdx.x & 63;
-    const bool lead = (lane & 1) == 0;
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // variables 16t .. 16t+15
-    const uint32_t w = (uint32_t)(t >> 1);
-    const bool live = w < b.n_words;  // (cover and thr are padded to whole words with zeros)
-    uint32_t a = 0, biased = 0;
-    uint4 key = make_uint4(0u, 0u, 0u, 0u);
-    uint4 c = make_uint4(0u, 0u, 0u, 0u);
-    if (live) {
-        if (lead) a = b.A[w];
-        key = reinterpret_cast<const uint4*>(g.words)[w];
-        biased = (wbias[w >> 5] >> (w & 31u)) & 1u;
-        c = reinterpret_cast<const uint4*>(b.cover)[t];
-    }
-    const uint32_t active = st->active, stamp = st->stamp;
-    const uint64_t it = st->n_iter - 1;
-    spec_fence();
-    if (!active) return;
-    const uint32_t cs[4] = {c.x, c.y, c.z, c.w};
-    uint32_t x = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) x |= (uint32_t)(((cs[i >> 2] >> (8 * (i & 3))) & 0xFFu) == stamp) << i;
-    if (x && biased)
-        x |= biased_draw16(reinterpret_cast<const uint4*>(b.thr) + 4 * t, 8u * key.z + 4u * (uint32_t)(lane & 1), it,
-                           key.x, key.y) << 16;
-    const uint32_t y = __shfl_xor(x, 1, 64);
-    const uint32_t cm = (x & 0xFFFFu) | (y << 16);
-    if (lead && cm) {
-        const uint32_t bits = biased ? (x >> 16) | (y & 0xFFFF0000u)
-                                     : philox_x(key.z, (uint32_t)it, 0u, (uint32_t)(it >> 32), key.x, key.y);
-        b.A[w] = (a & ~cm) | (bits & cm);
-    }
+    resample_body<true, true>(b, g.words, wbias);
 }
 
 // Allreduce exchange (ALLL_FLAG_EXCHANGE_ALLREDUCE): each rank resamples only the MIS clauses
@@ -2456,7 +2381,7 @@ __device__ __forceinline__ void delta_clause(const ClauseView& cv, uint32_t* del
         bool dup = false;
         for (uint64_t q = lb; q < j; ++q) dup |= (lvar(cv, q) == v);
         if (dup) continue;
-        const uint32_t nb = (philox_x(v >> 5, (uint32_t)it, 0u, (uint32_t)(it >> 32), k0, k1) >> (v & 31u)) & 1u;
+        const uint32_t nb = (resample_word(k0, k1, it, v >> 5) >> (v & 31u)) & 1u;
         if (nb != (l & 1u)) atomicXor(&delta[v >> 5], 1u << (v & 31u));
     }
 }

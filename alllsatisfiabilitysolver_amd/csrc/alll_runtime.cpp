@@ -11,7 +11,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstddef>
 #include <cstdlib>
 #include <cstdio>
@@ -24,30 +23,13 @@
 #include "alll_group_dev.h"
 #include "alll_internal.h"
 #include "alll_layout.h"
+#include "alll_rt_util.h"
 
 using namespace alll;
 
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess)                                                            \
-            return fail(ALLL_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                        __FILE__, __LINE__);                                             \
-    } while (0)
 
 #define NCCL_TRY(expr)                                                                    \
     do {                                                                                  \

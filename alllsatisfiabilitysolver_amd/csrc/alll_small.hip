@@ -15,7 +15,7 @@
 // Two instantiations of one body: k_small for a batch without per-variable thresholds, k_small_biased
 // for a batch in which at least one item has some.
 #include "alll_small.h"
-#include "alll_philox.h"
+#include "alll_draws.h"
 
 namespace alll {
 
@@ -44,24 +44,24 @@ struct SmallThr {
     bool on, in_lds;
 };
 
-// clause [j0, j1) joins the MIS: its variables are covered (claim word 0) and resampled.  BIASED and
-// an item with thresholds: variable v draws element v & 3 of the call {v >> 2, it, 1} and is 1 below
-// its threshold (0xFFFFFFFF: always); a variable that occurs twice is drawn twice to the same value.
+// clause [j0, j1) joins the MIS: its variables are covered (claim word 0) and resampled in round
+// {it_lo, it_hi} (the loop holds the round as the two words: k_small's machine code depends on it).
+// BIASED and an item with thresholds: every variable takes its own biased draw (alll_draws.h); a
+// variable that occurs twice is drawn twice to the same value.
 template <bool BIASED>
 __device__ __forceinline__ void small_join(uint32_t* s_claim, uint32_t* s_A, uint32_t* s_ctl, const uint16_t* s_lits,
                                            uint32_t j0, uint32_t j1, uint32_t it_lo, uint32_t it_hi, uint32_t k0,
                                            uint32_t k1, const SmallThr& T) {
+    const uint64_t it = (uint64_t)it_hi << 32 | it_lo;
     for (uint32_t j = j0; j < j1; ++j) {
         const uint32_t v = s_lits[j] >> 1, bit = 1u << (v & 31u);
         s_claim[v] = 0;
         bool one;
         if (BIASED && T.on) {
-            const uint4 q = philox_4(v >> 2, it_lo, 1u, it_hi, k0, k1);
-            const uint32_t e = v & 3u, x = e == 0 ? q.x : e == 1 ? q.y : e == 2 ? q.z : q.w;
-            const uint32_t t = T.in_lds ? T.lds[v] : T.glb[v];
-            one = (x < t) | (t == 0xFFFFFFFFu);
+            const uint32_t x = biased_resample_var(k0, k1, it, v);
+            one = biased_bit(x, T.in_lds ? T.lds[v] : T.glb[v]);
         } else {
-            one = (philox_x(v >> 5, it_lo, 0u, it_hi, k0, k1) & bit) != 0;
+            one = (resample_word(k0, k1, it, v >> 5) & bit) != 0;
         }
         if (one) atomicOr(&s_A[v >> 5], bit);
         else atomicAnd(&s_A[v >> 5], ~bit);
@@ -276,7 +276,7 @@ __global__ void __launch_bounds__(1024) k_small_biased(const SmallItem* __restri
 __global__ void k_small_init(const SmallItem* __restrict__ items, uint32_t* __restrict__ g_A) {
     const SmallItem it = items[blockIdx.x];
     for (uint32_t w = threadIdx.x; w < it.n_words; w += blockDim.x) {
-        uint32_t x = philox_x(w, 0u, 0xFFFFFFFFu, 0u, (uint32_t)it.seed, (uint32_t)(it.seed >> 32));
+        uint32_t x = fill_word((uint32_t)it.seed, (uint32_t)(it.seed >> 32), w);
         if (w == it.n_words - 1u && (it.n_vars & 31u)) x &= (1u << (it.n_vars & 31u)) - 1u;
         g_A[it.a_at + w] = x;
     }

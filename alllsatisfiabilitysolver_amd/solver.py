@@ -364,122 +364,24 @@ def batch_fits(n_vars: int, n_clauses: int, n_literals: int) -> bool:
     return bool(N.lib().alll_batch_fits(n_vars, n_clauses, n_literals))
 
 
-class BatchSolver:
-    """Owns one batch of LDS-resident instances (alll_batch): item i is problems[i] =
-    (n_vars, offsets, literals) with seeds[i], solved by one workgroup; entries of `problems`
-    may repeat the same arrays (many seeds of one instance), which the device then holds once.
-    Every item computes exactly what Solver(n_vars, offsets, literals, seed=seeds[i],
-    max_iters=max_iters) computes."""
+class _ItemSolver:
+    """What BatchSolver and GroupSolver share: item i is problems[i] = (n_vars, offsets, literals)
+    with seeds[i]; the entry points are alll_<_KIND>_*, the handle is self._h."""
 
-    def __init__(self, problems, seeds, max_iters: int = 0, device: int = -1):
+    _KIND = ""          # "batch" or "group"
+    _FIRST_SOLVED = 0   # the kind's ALLL_*_FIRST_SOLVED
+
+    def _fn(self, name: str):
+        return getattr(self._L, f"alll_{self._KIND}_{name}")
+
+    def __init__(self, problems, seeds, max_iters: int, device: int, flags: Optional[int]):
         self._L = N.lib()
         problems = list(problems)
         self._seeds = np.ascontiguousarray(seeds, np.uint64)
         if self._seeds.size != len(problems):
             raise ValueError(f"{len(problems)} problems, {self._seeds.size} seeds")
         self.n_items = len(problems)
-        # one converted copy per distinct pair of arrays: shared problems stay shared
-        self._keep = {}
-        arr = (N.Problem * max(1, self.n_items))()
-        self.n_vars = []
-        for i, (n_vars, offsets, literals) in enumerate(problems):
-            key = (id(offsets), id(literals))
-            if key not in self._keep:
-                self._keep[key] = (offsets, literals, np.ascontiguousarray(offsets, np.uint64),
-                                   np.ascontiguousarray(literals, np.uint32))
-            _, _, offs, lits = self._keep[key]
-            arr[i] = N.Problem(int(n_vars), 0, max(0, offs.size - 1), _p(offs, _u64p), _p(lits, _u32p))
-            self.n_vars.append(int(n_vars))
-        opt = N.Options()
-        self._L.alll_default_options(ctypes.byref(opt))
-        opt.max_iters, opt.device = max_iters, device
-        self._b = ctypes.c_void_p()
-        N.check(self._L.alll_batch_create(arr, _p(self._seeds, _u64p), self.n_items, ctypes.byref(opt),
-                                          ctypes.byref(self._b)), "alll_batch_create")
-        self._keep = None  # (the library keeps no caller pointer)
-
-    def close(self):
-        if getattr(self, "_b", None) and self._b.value:
-            self._L.alll_batch_destroy(self._b)
-            self._b = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def solve(self, first_solved: bool = False) -> List[dict]:
-        """Runs every item until it is solved or capped; one dict per item: the statistics and
-        "status" (ALLL_OK or ALLL_ERR_MAX_ITERS).  first_solved: return after the first slice
-        in which an item became solved; a later call continues."""
-        st = (N.Stats * self.n_items)()
-        status = (ctypes.c_int32 * self.n_items)()
-        N.check(self._L.alll_batch_solve(self._b, N.BATCH_FIRST_SOLVED if first_solved else 0, st, status),
-                "alll_batch_solve")
-        return [dict(st[i].as_dict(), status=int(status[i])) for i in range(self.n_items)]
-
-    def run(self, n_iters: int) -> List[dict]:
-        """n_iters more full iterations of every unfinished item (Solver.run for each)."""
-        st = (N.Stats * self.n_items)()
-        N.check(self._L.alll_batch_run(self._b, n_iters, st), "alll_batch_run")
-        return [st[i].as_dict() for i in range(self.n_items)]
-
-    def stats(self, i: int) -> dict:
-        st = N.Stats()
-        N.check(self._L.alll_batch_get_stats(self._b, i, ctypes.byref(st)), "alll_batch_get_stats")
-        return st.as_dict()
-
-    def assignment_words(self, i: int) -> np.ndarray:
-        w = np.zeros((self.n_vars[i] + 31) // 32, np.uint32)
-        N.check(self._L.alll_batch_get_assignment_words(self._b, i, _p(w, _u32p), w.size), "batch get_assignment")
-        return w
-
-    def set_assignment_words(self, i: int, w):
-        w = np.ascontiguousarray(w, np.uint32)
-        N.check(self._L.alll_batch_set_assignment_words(self._b, i, _p(w, _u32p), w.size), "batch set_assignment")
-
-    def set_slice(self, n: int):
-        """Iterations per kernel launch (0: the default)."""
-        N.check(self._L.alll_batch_set_slice(self._b, n), "alll_batch_set_slice")
-
-    def set_probabilities(self, i: int, p):
-        """Solver.set_probabilities for item i: it then computes what a Solver with seeds[i] and the
-        same probabilities computes.  Items that are one instance under different pinned variables
-        and solve(first_solved=True) make a cube portfolio (solve_cubes)."""
-        self.set_thresholds(i, None if p is None else var_thresholds(p))
-
-    def set_thresholds(self, i: int, thr):
-        """alll_batch_set_var_thresholds: the item's n_vars uint32 thresholds, or None."""
-        if thr is None:
-            N.check(self._L.alll_batch_set_var_thresholds(self._b, i, None, 0), "batch set_var_thresholds")
-            return
-        thr = np.ascontiguousarray(thr, np.uint32)
-        N.check(self._L.alll_batch_set_var_thresholds(self._b, i, _p(thr, _u32p), thr.size), "batch set_var_thresholds")
-
-
-class GroupSolver:
-    """Owns one block-diagonal group (alll_group): item i is problems[i] = (n_vars, offsets,
-    literals) with seeds[i], of any size; the items are laid side by side as one instance and the
-    one-instance loop advances all of them together.  Every item computes exactly what
-    Solver(n_vars, offsets, literals, seed=seeds[i], max_iters=max_iters) computes.  flags: the
-    FLAG_* that do not change results (NO_GRAPH, GENERIC_CSR, NO_RANGED, KERNEL_TIMING,
-    ATOMIC_CLAIMS)."""
-
-    def __init__(self, problems, seeds, max_iters: int = 0, device: int = -1, flags: int = 0):
-        self._L = N.lib()
-        problems = list(problems)
-        self._seeds = np.ascontiguousarray(seeds, np.uint64)
-        if self._seeds.size != len(problems):
-            raise ValueError(f"{len(problems)} problems, {self._seeds.size} seeds")
-        self.n_items = len(problems)
-        keep = {}  # one converted copy per distinct pair of arrays
+        keep = {}  # one converted copy per distinct pair of arrays: shared problems stay shared
         arr = (N.Problem * max(1, self.n_items))()
         self.n_vars = []
         for i, (n_vars, offsets, literals) in enumerate(problems):
@@ -492,16 +394,18 @@ class GroupSolver:
             self.n_vars.append(int(n_vars))
         opt = N.Options()
         self._L.alll_default_options(ctypes.byref(opt))
-        opt.max_iters, opt.device, opt.flags = max_iters, device, flags
-        self._g = ctypes.c_void_p()
-        N.check(self._L.alll_group_create(arr, _p(self._seeds, _u64p), self.n_items, ctypes.byref(opt),
-                                          ctypes.byref(self._g)), "alll_group_create")
+        opt.max_iters, opt.device = max_iters, device
+        if flags is not None:  # (None: the default options' flags)
+            opt.flags = flags
+        self._h = ctypes.c_void_p()
+        N.check(self._fn("create")(arr, _p(self._seeds, _u64p), self.n_items, ctypes.byref(opt), ctypes.byref(self._h)),
+                f"alll_{self._KIND}_create")
         # (the library keeps no caller pointer)
 
     def close(self):
-        if getattr(self, "_g", None) and self._g.value:
-            self._L.alll_group_destroy(self._g)
-            self._g = ctypes.c_void_p()
+        if getattr(self, "_h", None) and self._h.value:
+            self._fn("destroy")(self._h)
+            self._h = ctypes.c_void_p()
 
     def __del__(self):
         try:
@@ -516,56 +420,97 @@ class GroupSolver:
         self.close()
 
     def solve(self, first_solved: bool = False) -> List[dict]:
-        """Runs every item until it is solved or capped; one dict per item: the statistics and
-        "status" (ALLL_OK or ALLL_ERR_MAX_ITERS).  first_solved: return once at least one item
-        is solved (the winner: the solved item with the fewest iterations, the lowest index on a
-        tie); a later call continues."""
         st = (N.Stats * self.n_items)()
         status = (ctypes.c_int32 * self.n_items)()
-        N.check(self._L.alll_group_solve(self._g, N.GROUP_FIRST_SOLVED if first_solved else 0, st, status),
-                "alll_group_solve")
+        N.check(self._fn("solve")(self._h, self._FIRST_SOLVED if first_solved else 0, st, status),
+                f"alll_{self._KIND}_solve")
         return [dict(st[i].as_dict(), status=int(status[i])) for i in range(self.n_items)]
 
     def run(self, n_iters: int) -> List[dict]:
         """n_iters more full iterations of every unfinished item (Solver.run for each)."""
         st = (N.Stats * self.n_items)()
-        N.check(self._L.alll_group_run(self._g, n_iters, st), "alll_group_run")
+        N.check(self._fn("run")(self._h, n_iters, st), f"alll_{self._KIND}_run")
         return [st[i].as_dict() for i in range(self.n_items)]
 
     def stats(self, i: int) -> dict:
         st = N.Stats()
-        N.check(self._L.alll_group_get_stats(self._g, i, ctypes.byref(st)), "alll_group_get_stats")
+        N.check(self._fn("get_stats")(self._h, i, ctypes.byref(st)), f"alll_{self._KIND}_get_stats")
         return st.as_dict()
 
     def assignment_words(self, i: int) -> np.ndarray:
         w = np.zeros((self.n_vars[i] + 31) // 32, np.uint32)
-        N.check(self._L.alll_group_get_assignment_words(self._g, i, _p(w, _u32p), w.size), "group get_assignment")
+        N.check(self._fn("get_assignment_words")(self._h, i, _p(w, _u32p), w.size), f"{self._KIND} get_assignment")
         return w
 
     def set_assignment_words(self, i: int, w):
         w = np.ascontiguousarray(w, np.uint32)
-        N.check(self._L.alll_group_set_assignment_words(self._g, i, _p(w, _u32p), w.size), "group set_assignment")
+        N.check(self._fn("set_assignment_words")(self._h, i, _p(w, _u32p), w.size), f"{self._KIND} set_assignment")
 
     def set_probabilities(self, i: int, p):
         """Solver.set_probabilities for item i: it then computes what a Solver with seeds[i] and the
         same probabilities computes.  Items that are one instance under different pinned variables
-        and solve(first_solved=True) make a cube portfolio."""
+        and solve(first_solved=True) make a cube portfolio (solve_cubes)."""
         self.set_thresholds(i, None if p is None else var_thresholds(p))
 
     def set_thresholds(self, i: int, thr):
-        """alll_group_set_var_thresholds: the item's n_vars uint32 thresholds, or None."""
+        """alll_batch_set_var_thresholds / alll_group_set_var_thresholds: the item's n_vars uint32
+        thresholds, or None."""
         if thr is None:
-            N.check(self._L.alll_group_set_var_thresholds(self._g, i, None, 0), "group set_var_thresholds")
+            N.check(self._fn("set_var_thresholds")(self._h, i, None, 0), f"{self._KIND} set_var_thresholds")
             return
         thr = np.ascontiguousarray(thr, np.uint32)
-        N.check(self._L.alll_group_set_var_thresholds(self._g, i, _p(thr, _u32p), thr.size), "group set_var_thresholds")
+        N.check(self._fn("set_var_thresholds")(self._h, i, _p(thr, _u32p), thr.size), f"{self._KIND} set_var_thresholds")
+
+
+class BatchSolver(_ItemSolver):
+    """Owns one batch of LDS-resident instances (alll_batch): item i is problems[i] =
+    (n_vars, offsets, literals) with seeds[i], solved by one workgroup; entries of `problems`
+    may repeat the same arrays (many seeds of one instance), which the device then holds once.
+    Every item computes exactly what Solver(n_vars, offsets, literals, seed=seeds[i],
+    max_iters=max_iters) computes."""
+
+    _KIND, _FIRST_SOLVED = "batch", N.BATCH_FIRST_SOLVED
+
+    def __init__(self, problems, seeds, max_iters: int = 0, device: int = -1):
+        super().__init__(problems, seeds, max_iters, device, None)
+
+    def solve(self, first_solved: bool = False) -> List[dict]:
+        """Runs every item until it is solved or capped; one dict per item: the statistics and
+        "status" (ALLL_OK or ALLL_ERR_MAX_ITERS).  first_solved: return after the first slice
+        in which an item became solved; a later call continues."""
+        return super().solve(first_solved)
+
+    def set_slice(self, n: int):
+        """Iterations per kernel launch (0: the default)."""
+        N.check(self._L.alll_batch_set_slice(self._h, n), "alll_batch_set_slice")
+
+
+class GroupSolver(_ItemSolver):
+    """Owns one block-diagonal group (alll_group): item i is problems[i] = (n_vars, offsets,
+    literals) with seeds[i], of any size; the items are laid side by side as one instance and the
+    one-instance loop advances all of them together.  Every item computes exactly what
+    Solver(n_vars, offsets, literals, seed=seeds[i], max_iters=max_iters) computes.  flags: the
+    FLAG_* that do not change results (NO_GRAPH, GENERIC_CSR, NO_RANGED, KERNEL_TIMING,
+    ATOMIC_CLAIMS)."""
+
+    _KIND, _FIRST_SOLVED = "group", N.GROUP_FIRST_SOLVED
+
+    def __init__(self, problems, seeds, max_iters: int = 0, device: int = -1, flags: int = 0):
+        super().__init__(problems, seeds, max_iters, device, flags)
+
+    def solve(self, first_solved: bool = False) -> List[dict]:
+        """Runs every item until it is solved or capped; one dict per item: the statistics and
+        "status" (ALLL_OK or ALLL_ERR_MAX_ITERS).  first_solved: return once at least one item
+        is solved (the winner: the solved item with the fewest iterations, the lowest index on a
+        tie); a later call continues."""
+        return super().solve(first_solved)
 
     def layout(self) -> int:
         """Layout of the union: 0 generic CSR, k > 0 fixed width k."""
-        return int(self._L.alll_group_layout(self._g))
+        return int(self._L.alll_group_layout(self._h))
 
     def eval_kernel(self) -> str:
-        return self._L.alll_group_eval_kernel(self._g).decode()
+        return self._L.alll_group_eval_kernel(self._h).decode()
 
 
 def solve_portfolio(n_vars: int, offsets, literals, seeds, max_iters: int = 0):
