@@ -63,6 +63,8 @@ EXPORTED = [
     "alll_group_eval_kernel",
     "alll_var_threshold", "alll_biased_initial_assignment", "alll_set_var_thresholds",
     "alll_group_set_var_thresholds", "alll_batch_set_var_thresholds", "alll_pinned_conflict",
+    "alll_track_best", "alll_get_best", "alll_group_track_best", "alll_group_get_best",
+    "alll_batch_track_best", "alll_batch_get_best",
 ]
 
 
@@ -207,6 +209,12 @@ _SIGS = {
     "alll_group_set_var_thresholds": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
     "alll_batch_set_var_thresholds": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
     "alll_pinned_conflict": ([ctypes.POINTER(Problem), _u32p, ctypes.c_uint64, _u64p], ctypes.c_int),
+    "alll_track_best": ([_vp, ctypes.c_int], ctypes.c_int),
+    "alll_get_best": ([_vp, _u64p, _u64p, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_group_track_best": ([_vp, ctypes.c_int], ctypes.c_int),
+    "alll_group_get_best": ([_vp, ctypes.c_uint64, _u64p, _u64p, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_batch_track_best": ([_vp, ctypes.c_int], ctypes.c_int),
+    "alll_batch_get_best": ([_vp, ctypes.c_uint64, _u64p, _u64p, _u32p, ctypes.c_uint64], ctypes.c_int),
 }
 
 _lib = None

@@ -36,9 +36,11 @@ struct SmallState {
     uint32_t n_violated;   // violated clauses of the last eval pass
     uint32_t done;         // 0 running, 1 solved, 2 stopped at limit_nores
     uint32_t rounds_max;   // most LFMIS rounds one iteration needed
-    uint32_t pad;
+    // best-assignment tracking (maintained by the tracked instantiations only)
+    uint32_t best_u;       // fewest violated clauses a pass found (~0: no pass yet)
+    uint64_t best_iter;    // n_iter of the first pass that found them (0: no pass yet)
 };
-static_assert(sizeof(SmallState) == 56, "SmallState");
+static_assert(sizeof(SmallState) == 64, "SmallState");
 
 // Dynamic LDS of the kernel: byte offsets of its arrays, sized from the largest item of the batch.
 struct SmallLds {

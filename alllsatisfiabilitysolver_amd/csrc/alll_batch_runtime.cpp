@@ -58,6 +58,7 @@ struct alll_batch {
     uint32_t max_vars = 0, max_clauses = 0, max_lits = 0, a_words = 0;
     bool thr_global = false;      // ALLL_BATCH_THR_GLOBAL: never the LDS copy
     std::vector<uint8_t> biased;  // per item
+    uint32_t* d_best = nullptr;   // best-assignment tracking: the records' words, d.best while it is on
 };
 
 namespace {
@@ -176,7 +177,10 @@ int alll_batch_create(const alll_problem* probs, const uint64_t* seeds, uint64_t
     if (hipHostMalloc((void**)&b->h_state, sizeof(SmallState) * n_items, 0) != hipSuccess)
         return bail(fail(ALLL_ERR_OOM, "hipHostMalloc failed"));
     memset(b->h_state, 0, sizeof(SmallState) * n_items);
-    for (uint64_t i = 0; i < n_items; ++i) b->h_state[i].limit_eval = b->h_state[i].limit_nores = ~0ull;
+    for (uint64_t i = 0; i < n_items; ++i) {
+        b->h_state[i].limit_eval = b->h_state[i].limit_nores = ~0ull;
+        b->h_state[i].best_u = ~0u;  // (no record yet)
+    }
     const SmallState* states = nullptr;
     const uint32_t* A = nullptr;
     const std::vector<uint32_t> zeros(plan.a_words, 0u);
@@ -319,6 +323,49 @@ int alll_batch_set_var_thresholds(alll_batch* b, uint64_t item, const uint32_t* 
     const bool in_lds = !b->thr_global && with.bytes <= SMALL_LDS_BUDGET;
     b->d.thr_lds = in_lds ? at : 0;
     b->d.lds_thr_bytes = with.bytes;
+    return ALLL_OK;
+}
+
+int alll_batch_track_best(alll_batch* b, int on) {
+    if (!b) return fail(ALLL_ERR_INVALID_ARG, "null batch");
+    HIP_TRY(hipSetDevice(b->device));
+    if (int rc = read_states(b)) return rc;  // (drains the stream)
+    for (uint32_t i = 0; i < b->d.n_items; ++i)
+        if (b->h_state[i].n_iter != 0)
+            return fail(ALLL_ERR_INVALID_ARG, "best-assignment tracking is switched before the batch's first iteration "
+                                              "(item %u has made %llu)", i, (unsigned long long)b->h_state[i].n_iter);
+    if (on && !b->d_best) {
+        void* q = nullptr;
+        const size_t bytes = std::max<size_t>((size_t)b->a_words * 4, 16);
+        if (hipMalloc(&q, bytes) != hipSuccess) return fail(ALLL_ERR_OOM, "hipMalloc(%zu bytes) failed", bytes);
+        b->allocs.push_back(q);
+        HIP_TRY(hipMemset(q, 0, bytes));
+        b->d_best = static_cast<uint32_t*>(q);
+    }
+    b->d.best = on ? b->d_best : nullptr;  // (no item has made a pass: every record is still empty)
+    return ALLL_OK;
+}
+
+int alll_batch_get_best(alll_batch* b, uint64_t item, uint64_t* n_violated, uint64_t* iteration, uint32_t* words,
+                        uint64_t n_words) {
+    if (!b) return fail(ALLL_ERR_INVALID_ARG, "null batch");
+    if (item >= b->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, b->d.n_items);
+    if (!b->d.best)
+        return fail(ALLL_ERR_INVALID_ARG, "best assignment: the batch does not track it (alll_batch_track_best before "
+                                          "the first iteration)");
+    const SmallItem& it = b->items[item];
+    if (words && n_words != it.n_words)
+        return fail(ALLL_ERR_INVALID_ARG, "best assignment: %llu words for the %u of item %llu",
+                    (unsigned long long)n_words, it.n_words, (unsigned long long)item);
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    SmallState s;
+    HIP_TRY(hipMemcpy(&s, b->d.states + item, sizeof s, hipMemcpyDeviceToHost));
+    if (n_violated) *n_violated = s.best_iter ? s.best_u : ~0ull;
+    if (iteration) *iteration = s.best_iter;
+    // (before any pass the words are left untouched)
+    if (words && s.best_iter && it.n_words)
+        HIP_TRY(hipMemcpy(words, b->d.best + it.a_at, it.n_words * 4ull, hipMemcpyDeviceToHost));
     return ALLL_OK;
 }
 

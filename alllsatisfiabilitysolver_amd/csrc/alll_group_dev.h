@@ -34,14 +34,25 @@ struct GroupDev {
     uint32_t pad;
 };
 
+// Best-assignment tracking of a group: passed to the tracked kernels only, so the
+// kernels of a group that does not track keep their arguments.  The words of the records are
+// LoopBuffers::A_best (the union's, an item's at its word base).
+struct GroupBest {
+    unsigned long long* rec;    // per item {fewest violated clauses of a pass (~0: none yet), that pass}
+    uint32_t* improved;         // per item: the current pass is its record (k_group_best)
+    const uint32_t* word_item;  // per assignment word of the union: its item
+};
+
 // Launchers (alll_kernels.hip).  All asynchronous on `s`.
 hipError_t launch_group_init(const LoopBuffers& b, const GroupDev& g, hipStream_t s);
 // after the LFMIS tail: the pass's violated clauses and MIS clauses counted per item
 hipError_t launch_group_account(const ClauseView& cv, const LoopBuffers& b, const GroupDev& g, hipStream_t s);
 // the keyed resample (in place of k_resample_vars) and, in one more workgroup, the items' states;
 // wbias (with b.thr): a bit per assignment word, set for the words of the items
-// that have thresholds -- k_group_resample_biased; nullptr: k_group_resample
-hipError_t launch_group_resample(const LoopBuffers& b, const GroupDev& g, const uint32_t* wbias, hipStream_t s);
+// that have thresholds -- k_group_resample_biased; nullptr: k_group_resample.  gb (with b.A_best):
+// k_group_best, then the tracked forms of the two
+hipError_t launch_group_resample(const LoopBuffers& b, const GroupDev& g, const uint32_t* wbias, const GroupBest* gb,
+                                 hipStream_t s);
 
 }  // namespace alll
 
@@ -72,5 +83,10 @@ void ctx_assignment_changed(alll_ctx* c);  // the next pass's violated count is 
 // iterations hold the old pointers by value and are dropped.  Stream drained by the caller.
 int ctx_bias_supported(alll_ctx* c);
 void ctx_set_group_bias(alll_ctx* c, const uint32_t* thr, const uint32_t* wbias);
+// best-assignment tracking of a group: the same option check under the feature's
+// name, then the union's record words (the context allocates them) and the group's tables, or
+// nullptr for off; captured iterations are dropped.  Stream drained by the caller, no iteration made.
+int ctx_track_supported(alll_ctx* c);
+int ctx_set_group_best(alll_ctx* c, const GroupBest* gb);
 
 }  // namespace alll

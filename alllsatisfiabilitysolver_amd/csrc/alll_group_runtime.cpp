@@ -34,6 +34,10 @@ struct alll_group {
     const uint32_t* d_wbias = nullptr;
     std::vector<uint32_t> wbias;   // host copy
     std::vector<uint8_t> biased;   // per item
+    // best-assignment tracking, allocated at the first alll_group_track_best(on):
+    // the items' records and flags and the item of every word (the context keeps a pointer to it)
+    GroupBest best{};
+    bool tracking = false;
 };
 
 namespace {
@@ -280,6 +284,64 @@ int alll_group_set_var_thresholds(alll_group* g, uint64_t item, const uint32_t* 
         hipStreamSynchronize(g->stream) != hipSuccess)
         return fail(ALLL_ERR_HIP, "fill kernel failed: %s", hipGetErrorString(hipGetLastError()));
     ctx_assignment_changed(g->ctx);
+    return ALLL_OK;
+}
+
+int alll_group_track_best(alll_group* g, int on) {
+    if (!g) return fail(ALLL_ERR_INVALID_ARG, "null group");
+    int rc;
+    if ((rc = ctx_track_supported(g->ctx))) return rc;
+    HIP_TRY(hipSetDevice(g->device));
+    if ((rc = read_all(g))) return rc;  // (drains the stream)
+    const CtxAccess a = ctx_access(g->ctx);
+    if (a.h_state->n_iter != 0)
+        return fail(ALLL_ERR_INVALID_ARG, "best-assignment tracking is switched before the group's first iteration "
+                                          "(%llu made)", (unsigned long long)a.h_state->n_iter);
+    const uint32_t n = g->d.n_items;
+    if (on && !g->best.rec) {
+        std::vector<uint32_t> word_item(a.b->n_words, 0u);
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t w = 0; w < g->items[i].n_words; ++w) word_item[g->items[i].word_base + w] = i;
+        const unsigned long long* rec = nullptr;
+        const uint32_t* improved = nullptr;
+        if ((rc = upload<unsigned long long>(g, &rec, nullptr, (size_t)n * 2)) ||
+            (rc = upload<uint32_t>(g, &improved, nullptr, (size_t)n)) ||
+            (rc = upload(g, &g->best.word_item, word_item.data(), word_item.size())))
+            return rc;
+        g->best.rec = const_cast<unsigned long long*>(rec);
+        g->best.improved = const_cast<uint32_t*>(improved);
+    }
+    if (on) {  // empty records: {~0, 0} per item, no flag
+        std::vector<unsigned long long> rec((size_t)n * 2, 0ull);
+        for (uint32_t i = 0; i < n; ++i) rec[2 * (size_t)i] = ~0ull;
+        if (n) HIP_TRY(hipMemcpy(g->best.rec, rec.data(), rec.size() * 8, hipMemcpyHostToDevice));
+        if (n) HIP_TRY(hipMemset(g->best.improved, 0, (size_t)n * 4));
+    }
+    if ((rc = ctx_set_group_best(g->ctx, on ? &g->best : nullptr))) return rc;
+    g->tracking = on != 0;
+    return ALLL_OK;
+}
+
+int alll_group_get_best(alll_group* g, uint64_t item, uint64_t* n_violated, uint64_t* iteration, uint32_t* words,
+                        uint64_t n_words) {
+    if (!g) return fail(ALLL_ERR_INVALID_ARG, "null group");
+    if (item >= g->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, g->d.n_items);
+    if (!g->tracking)
+        return fail(ALLL_ERR_INVALID_ARG, "best assignment: the group does not track it (alll_group_track_best before "
+                                          "the first iteration)");
+    const GroupItem& it = g->items[item];
+    if (words && n_words != it.n_words)
+        return fail(ALLL_ERR_INVALID_ARG, "best assignment: %llu words for the %u of item %llu",
+                    (unsigned long long)n_words, it.n_words, (unsigned long long)item);
+    HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    unsigned long long rec[2];
+    HIP_TRY(hipMemcpy(rec, g->best.rec + 2 * item, sizeof rec, hipMemcpyDeviceToHost));
+    if (n_violated) *n_violated = rec[0];
+    if (iteration) *iteration = rec[1];
+    // (before any pass the words are left untouched)
+    if (words && rec[1] && it.n_words)
+        HIP_TRY(hipMemcpy(words, ctx_access(g->ctx).b->A_best + it.word_base, it.n_words * 4ull, hipMemcpyDeviceToHost));
     return ALLL_OK;
 }
 

@@ -183,6 +183,12 @@ struct DevState {
     uint32_t rd_n;         // reference-RNG mode: engine positions the parallel draws consider
     uint32_t rd_fail;      // reference-RNG mode: the parallel draws ran past rd_n (sequential redo)
     uint32_t rd_pad;
+    // best-assignment tracking (maintained by the reduce while LoopBuffers::A_best is set)
+    uint64_t best_u;       // fewest violated clauses an eval pass of the loop found (~0: no pass yet)
+    uint64_t best_iter;    // n_iter of the first pass that found them (0: no pass yet)
+    uint32_t improved;     // the current pass is that pass: the resample kernel copies the words it
+                           // loads to A_best before it changes them (0 once the loop's gate has closed)
+    uint32_t best_pad;
 };
 
 // Clause storage on the device.
@@ -376,6 +382,9 @@ struct LoopBuffers {
     // n_vars (a lane loads the 16 of its stamps unguarded); nullptr = the unbiased stream.  In a
     // group: the union's, read only for the words of biased items
     const uint32_t* thr;
+    // best-assignment tracking: n_words words, the assignment of the pass
+    // DevState::best_iter (in a group: per item, GroupBest); nullptr = off, the untracked kernels
+    uint32_t* A_best;
 };
 
 // LDS of k_fp_bbuild for a bucket of `width` variables: counters, list starts, first claimants

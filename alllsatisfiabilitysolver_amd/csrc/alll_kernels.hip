@@ -14,7 +14,9 @@
 //              SATInstance.h:391-451; dependency = shared variable, :369-389).
 //   k_resample_vars  Philox4x32-10 resampling of every variable of every MIS clause
 //              (resample_clauses, SATInstance.h:340-365), one pass over the variables;
-//              k_resample_biased when the variables have their own probabilities.
+//              k_resample_biased when the variables have their own probabilities;
+//              k_resample_vars_best / k_resample_biased_best when the context keeps the best
+//              assignment seen.
 // Integer / bit work only: no MFMA.  HBM-bound on the literal stream of k_eval.
 #include <algorithm>
 #include <atomic>
@@ -1073,6 +1075,14 @@ __device__ void reduce_body(const LoopBuffers& b, int mode) {
     if (u == 0) { st->done = 1; st->active = 0; }
     else if (st->n_iter >= st->limit_nores) { st->done = 2; st->active = 0; }
     else st->active = 1;
+    if (b.A_best) {
+        // best-assignment tracking: this pass -- the solved and the capped one
+        // included -- is the record when it found strictly fewer violated clauses than every pass
+        // before it; the resample kernel then copies the words it evaluated
+        const uint32_t better = u < st->best_u ? 1u : 0u;
+        if (better) { st->best_u = u; st->best_iter = st->n_iter; }
+        st->improved = better;
+    }
     if (b.stream_batch && u) {
         // streaming window of this iteration: the first one takes all m steps; later ones
         // m - k0, k0 = first violated clause index + 1 (where the reference's end-of-iteration
@@ -1153,6 +1163,8 @@ __global__ __launch_bounds__(1024) void k_reduce(LoopBuffers b, int mode) {
     if (mode == 0 && eval_gate_closed(b.state)) {
         if (threadIdx.x == 0) {
             b.state->active = 0;
+            // (the last pass's resample has run: a replay's resample kernel must not copy what it left)
+            if (b.A_best) b.state->improved = 0;
             if (b.fp_ctl) b.fp_ctl->state = FP_OFF;
         }
         return;
@@ -1865,7 +1877,10 @@ __global__ __launch_bounds__(T, (U <= BRS_UNROLL_NARROW && T <= 512) ? 2 : 1) vo
     if (fused_reduce && blockIdx.x == 0) {  // (no extra workgroup: every CU may hold a bucket)
         __syncthreads();
         if (eval_gate_closed(b.state)) {
-            if (threadIdx.x == 0) b.state->active = 0;
+            if (threadIdx.x == 0) {
+                b.state->active = 0;
+                if (b.A_best) b.state->improved = 0;  // (as k_reduce)
+            }
         } else {
             reduce_body(b, 0);
         }
@@ -2180,8 +2195,14 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tail(ClauseView cv, LoopBuffer
 //          the word, or with BIASED by both lanes, as both draw -- the calls of a word's half are
 //          8 * local word + 4 * half + 0..3 -- and bit w % 32 of wbias[w / 32] says whether word w's
 //          item has thresholds; a word of an unbiased item takes the one-call draw, bit for bit.
-template <bool GROUP, bool BIASED>
-__device__ __forceinline__ void resample_body(const LoopBuffers& b, const GroupWord* words, const uint32_t* wbias) {
+//   TRACK  (best-assignment tracking, DESIGN.md §4.9: LoopBuffers::A_best): when the pass is the best
+//          so far (DevState::improved; in a group the flag of the word's item, GroupBest), the lead
+//          lane stores the word it has loaded -- the assignment the pass evaluated -- to A_best, before
+//          the test of `active`: the solved and the capped pass resample nothing and are copied too.
+//          No launch and no load of the assignment beyond the kernel's own.
+template <bool GROUP, bool BIASED, bool TRACK = false>
+__device__ __forceinline__ void resample_body(const LoopBuffers& b, const GroupWord* words, const uint32_t* wbias,
+                                              const GroupBest& gb = GroupBest{}) {
     const DevState* st = b.state;
     const int lane = threadIdx.x & 63;
     const bool lead = (lane & 1) == 0;
@@ -2210,7 +2231,18 @@ __device__ __forceinline__ void resample_body(const LoopBuffers& b, const GroupW
     }
     const uint32_t active = st->active, stamp = st->stamp;
     const uint64_t it = st->n_iter - 1;
+    uint32_t improved = 0;
+    if constexpr (TRACK) {
+        if constexpr (GROUP) {
+            if (lead && live) improved = gb.improved[gb.word_item[w]];
+        } else {
+            improved = st->improved;
+        }
+    }
     spec_fence();
+    if constexpr (TRACK) {
+        if (lead && live && improved) b.A_best[w] = a;
+    }
     if (!active) return;
     const uint32_t cs[4] = {c.x, c.y, c.z, c.w};
     uint32_t x = 0;  // bit i: variable 16t + i is covered
@@ -2236,6 +2268,13 @@ __device__ __forceinline__ void resample_body(const LoopBuffers& b, const GroupW
 
 __global__ __launch_bounds__(256) void k_resample_vars(LoopBuffers b) { resample_body<false, false>(b, nullptr, nullptr); }
 __global__ __launch_bounds__(256) void k_resample_biased(LoopBuffers b) { resample_body<false, true>(b, nullptr, nullptr); }
+// ... with best-assignment tracking (launch_resample picks them when b.A_best is set)
+__global__ __launch_bounds__(256) void k_resample_vars_best(LoopBuffers b) {
+    resample_body<false, false, true>(b, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void k_resample_biased_best(LoopBuffers b) {
+    resample_body<false, true, true>(b, nullptr, nullptr);
+}
 
 // ------------------------------------------------------------------------------------
 // Block-diagonal groups (alll_group_dev.h): the union of the items runs the loop
@@ -2365,6 +2404,38 @@ __global__ __launch_bounds__(256) void k_group_resample(LoopBuffers b, GroupDev 
 __global__ __launch_bounds__(256) void k_group_resample_biased(LoopBuffers b, GroupDev g, const uint32_t* wbias) {
     if (blockIdx.x == gridDim.x - 1) { group_finish(b, g); return; }
     resample_body<true, true>(b, g.words, wbias);
+}
+
+// Best-assignment tracking of a group.  An item's violated count of a pass is
+// complete after k_group_account and is consumed by group_finish, which runs beside the resampling
+// lanes; k_group_best, a thread per item between the two kernels, compares it with the item's record
+// and leaves the item's flag for the lanes of the tracked resample kernels (word -> item:
+// GroupBest::word_item).  An ended item is never copied again; no pass since the last one
+// accounted (a replay after the loop's gate closed, whose resample has changed the words): every
+// flag is cleared.
+__global__ __launch_bounds__(256) void k_group_best(LoopBuffers b, GroupDev g, GroupBest gb) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g.n_items) return;
+    const uint64_t it = b.state->n_iter;
+    uint32_t better = 0;
+    if (it != g.ctl->acc_iter && g.items[i].end_iter == 0) {
+        const unsigned long long nv = g.scratch[(uint64_t)i * GROUP_SCRATCH];
+        if (nv < gb.rec[2 * i]) {
+            gb.rec[2 * i] = nv;
+            gb.rec[2 * i + 1] = it;
+            better = 1;
+        }
+    }
+    gb.improved[i] = better;
+}
+__global__ __launch_bounds__(256) void k_group_resample_best(LoopBuffers b, GroupDev g, GroupBest gb) {
+    if (blockIdx.x == gridDim.x - 1) { group_finish(b, g); return; }
+    resample_body<true, false, true>(b, g.words, nullptr, gb);
+}
+__global__ __launch_bounds__(256) void k_group_resample_biased_best(LoopBuffers b, GroupDev g, const uint32_t* wbias,
+                                                                    GroupBest gb) {
+    if (blockIdx.x == gridDim.x - 1) { group_finish(b, g); return; }
+    resample_body<true, true, true>(b, g.words, wbias, gb);
 }
 
 // Allreduce exchange (ALLL_FLAG_EXCHANGE_ALLREDUCE): each rank resamples only the MIS clauses
@@ -5596,6 +5667,11 @@ hipError_t launch_resample(const ClauseView& cv, const LoopBuffers& b, uint32_t 
     if (b.n_vars == 0) return hipSuccess;
     const uint64_t blocks = ((uint64_t)b.n_words * 2 + 255) / 256;  // a thread per 16 variables
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (b.A_best) {  // (best-assignment tracking)
+        if (b.thr) k_resample_biased_best<<<(uint32_t)blocks, 256, 0, s>>>(b);
+        else k_resample_vars_best<<<(uint32_t)blocks, 256, 0, s>>>(b);
+        return hipGetLastError();
+    }
     if (b.thr) k_resample_biased<<<(uint32_t)blocks, 256, 0, s>>>(b);  // (per-variable probabilities)
     else k_resample_vars<<<(uint32_t)blocks, 256, 0, s>>>(b);
     return hipGetLastError();
@@ -5626,10 +5702,17 @@ hipError_t launch_group_account(const ClauseView& cv, const LoopBuffers& b, cons
     return hipGetLastError();
 }
 
-hipError_t launch_group_resample(const LoopBuffers& b, const GroupDev& g, const uint32_t* wbias, hipStream_t s) {
+hipError_t launch_group_resample(const LoopBuffers& b, const GroupDev& g, const uint32_t* wbias, const GroupBest* gb,
+                                 hipStream_t s) {
     const uint64_t blocks = ((uint64_t)b.n_words * 2 + 255) / 256;  // a thread per 16 variables
     if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
     // + the workgroup of the items' states
+    if (gb && b.A_best) {  // (best-assignment tracking, DESIGN.md §4.9: the items' flags first)
+        if (g.n_items) k_group_best<<<(g.n_items + 255) / 256, 256, 0, s>>>(b, g, *gb);
+        if (wbias && b.thr) k_group_resample_biased_best<<<(uint32_t)blocks + 1, 256, 0, s>>>(b, g, wbias, *gb);
+        else k_group_resample_best<<<(uint32_t)blocks + 1, 256, 0, s>>>(b, g, *gb);
+        return hipGetLastError();
+    }
     if (wbias && b.thr) k_group_resample_biased<<<(uint32_t)blocks + 1, 256, 0, s>>>(b, g, wbias);
     else k_group_resample<<<(uint32_t)blocks + 1, 256, 0, s>>>(b, g);
     return hipGetLastError();

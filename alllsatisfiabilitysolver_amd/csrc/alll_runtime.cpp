@@ -126,6 +126,10 @@ struct alll_ctx {
     // points to it while they are set), and a group's per-word bits
     uint32_t* d_thr = nullptr;
     const uint32_t* grp_wbias = nullptr;
+    // best-assignment tracking: the record's words (b.A_best points to them while
+    // tracking is on), and a group's tables
+    uint32_t* d_best = nullptr;
+    const GroupBest* grp_best = nullptr;
 };
 
 namespace {
@@ -311,7 +315,7 @@ int enqueue_iteration(alll_ctx* c, hipEvent_t* marks, int variant) {
         HIP_TRY(launch_apply_delta(c->b, s));
     } else if (c->grp) {
         HIP_TRY(launch_group_account(c->cv, c->b, *c->grp, s));
-        HIP_TRY(launch_group_resample(c->b, *c->grp, c->grp_wbias, s));
+        HIP_TRY(launch_group_resample(c->b, *c->grp, c->grp_wbias, c->grp_best, s));
     } else {
         HIP_TRY(launch_resample(c->cv, c->b, c->own_begin, c->own_end, false, s));
     }
@@ -707,22 +711,47 @@ void drop_graphs(alll_ctx* c) {
     c->rr_graph.clear();
 }
 
-// Per-variable probabilities hook into the resample of the one-GPU loop only.
-int bias_supported(const alll_ctx* c) {
+// Per-variable probabilities and best-assignment tracking (§4.9) hook into the
+// resample kernels of the one-GPU loop only (resample_body): `what` names the feature in the message.
+int resample_hook_supported(const alll_ctx* c, const char* what) {
     if ((c->opt.flags & ALLL_FLAG_REFERENCE_RNG) || c->b.rrng_mask)
-        return fail(ALLL_ERR_UNSUPPORTED, "variable thresholds: ALLL_FLAG_REFERENCE_RNG draws the reference's own "
-                                          "fair-coin stream");
+        return fail(ALLL_ERR_UNSUPPORTED, "%s: ALLL_FLAG_REFERENCE_RNG draws the reference's own fair-coin stream "
+                                          "(its own resample kernels)", what);
     if ((c->opt.flags & ALLL_FLAG_EXCHANGE_ALLREDUCE) || c->allreduce)
-        return fail(ALLL_ERR_UNSUPPORTED, "variable thresholds: ALLL_FLAG_EXCHANGE_ALLREDUCE resamples through the "
-                                          "delta exchange, which draws fair coins only");
+        return fail(ALLL_ERR_UNSUPPORTED, "%s: ALLL_FLAG_EXCHANGE_ALLREDUCE resamples through the delta exchange, "
+                                          "which draws fair coins only", what);
     bool zero_id = true;
     for (int i = 0; i < 128; ++i) zero_id &= c->opt.comm_id[i] == 0;
     if (c->world != 1 || c->comm || !zero_id)
-        return fail(ALLL_ERR_UNSUPPORTED, "variable thresholds: one GPU only (world %d%s)", c->world,
+        return fail(ALLL_ERR_UNSUPPORTED, "%s: one GPU only (world %d%s)", what, c->world,
                     zero_id ? "" : ", a communicator id");
     if (c->opt.stream_batch != 0)
-        return fail(ALLL_ERR_UNSUPPORTED, "variable thresholds: the streaming solve (stream_batch %llu) is not covered",
+        return fail(ALLL_ERR_UNSUPPORTED, "%s: the streaming solve (stream_batch %llu) is not covered", what,
                     (unsigned long long)c->opt.stream_batch);
+    return ALLL_OK;
+}
+int bias_supported(const alll_ctx* c) { return resample_hook_supported(c, "variable thresholds"); }
+int track_supported(const alll_ctx* c) { return resample_hook_supported(c, "best-assignment tracking"); }
+
+// Switches the tracking of the best assignment: gb = a group's tables.  Before the
+// first iteration only: captured iterations hold LoopBuffers by value.
+int set_track_best(alll_ctx* c, bool on, const GroupBest* gb) {
+    int rc;
+    if ((rc = read_state(c))) return rc;  // (drains the stream)
+    if (c->h_state->n_iter != 0)
+        return fail(ALLL_ERR_INVALID_ARG, "best-assignment tracking is switched before the first iteration (%llu made)",
+                    (unsigned long long)c->h_state->n_iter);
+    if (on && !c->d_best) {
+        if ((rc = dalloc(c, &c->d_best, (size_t)c->b.n_words))) return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    c->b.A_best = on ? c->d_best : nullptr;
+    c->grp_best = on ? gb : nullptr;
+    c->h_state->best_u = ~0ull;
+    c->h_state->best_iter = 0;
+    c->h_state->improved = 0;
+    HIP_TRY(hipMemcpy(c->b.state, c->h_state, sizeof(DevState), hipMemcpyHostToDevice));
+    drop_graphs(c);  // (none is captured before the first iteration; one would hold the old pointer)
     return ALLL_OK;
 }
 
@@ -754,6 +783,8 @@ void ctx_set_group_bias(alll_ctx* c, const uint32_t* thr, const uint32_t* wbias)
     c->grp_wbias = wbias;
     drop_graphs(c);
 }
+int ctx_track_supported(alll_ctx* c) { return track_supported(c); }
+int ctx_set_group_best(alll_ctx* c, const GroupBest* gb) { return set_track_best(c, gb != nullptr, gb); }
 
 }  // namespace alll
 
@@ -1109,6 +1140,7 @@ int alll_create(const alll_problem* prob, const alll_options* opt_in, alll_ctx**
     c->h_state->limit_eval = ~0ull;
     c->h_state->limit_nores = ~0ull;
     c->h_state->round_next = 1;
+    c->h_state->best_u = ~0ull;
     if (lay.refrng) c->h_state->rd_state = opt.seed;  // (the random_device stand-in's state)
     if (hipMemcpyAsync(b.state, c->h_state, sizeof(DevState), hipMemcpyHostToDevice, c->stream) != hipSuccess)
         return bail(fail(ALLL_ERR_HIP, "state upload failed"));
@@ -1345,6 +1377,35 @@ int alll_set_var_thresholds(alll_ctx* c, const uint32_t* thr, uint64_t n) {
     HIP_TRY(launch_fill_words(b.A, b.n_words, b.n_vars, b.thr, b.seed, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     ctx_assignment_changed(c);
+    return ALLL_OK;
+}
+
+int alll_track_best(alll_ctx* c, int on) {
+    if (!c) return fail(ALLL_ERR_INVALID_ARG, "null context");
+    if (c->grp) return fail(ALLL_ERR_INVALID_ARG, "best-assignment tracking: the context belongs to a group "
+                                                  "(alll_group_track_best)");
+    int rc;
+    if ((rc = track_supported(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return set_track_best(c, on != 0, nullptr);
+}
+
+int alll_get_best(alll_ctx* c, uint64_t* n_violated, uint64_t* iteration, uint32_t* words, uint64_t n_words) {
+    if (!c) return fail(ALLL_ERR_INVALID_ARG, "null context");
+    if (c->grp) return fail(ALLL_ERR_INVALID_ARG, "best assignment: the context belongs to a group (alll_group_get_best)");
+    if (!c->b.A_best)
+        return fail(ALLL_ERR_INVALID_ARG, "best assignment: the context does not track it (alll_track_best before the "
+                                          "first iteration)");
+    if (words && n_words != c->b.n_words)
+        return fail(ALLL_ERR_INVALID_ARG, "best assignment: %llu words for the %u of the assignment",
+                    (unsigned long long)n_words, c->b.n_words);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = read_state(c)) return rc;  // (drains the stream)
+    if (n_violated) *n_violated = c->h_state->best_u;
+    if (iteration) *iteration = c->h_state->best_iter;
+    // (before any pass the words are left untouched)
+    if (words && c->h_state->best_iter && c->b.n_words)
+        HIP_TRY(hipMemcpy(words, c->b.A_best, c->b.n_words * 4ull, hipMemcpyDeviceToHost));
     return ALLL_OK;
 }
 

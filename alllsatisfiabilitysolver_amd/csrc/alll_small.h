@@ -23,6 +23,9 @@ struct SmallBatch {
     uint32_t thr_lds;        // byte offset of the LDS-resident thresholds behind lds, 0: the kernel reads the pool
     uint32_t lds_thr_bytes;  // dynamic LDS with them
     bool biased;             // an item has thresholds: the biased instantiation is launched
+    // best-assignment tracking (alll_batch_track_best): item i's record words at a_at of a
+    // second assignment pool; null: off, the untracked instantiations are launched
+    uint32_t* best;
 };
 
 // the dynamic LDS attribute of both instantiations of the kernel (on the batch's device, before its first slice)

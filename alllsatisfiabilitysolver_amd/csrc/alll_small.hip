@@ -73,13 +73,17 @@ __device__ __forceinline__ void small_join(uint32_t* s_claim, uint32_t* s_A, uin
 // The kernel's body.  BIASED = false is the kernel of a batch without thresholds (g_thr and thr_lds
 // unused); BIASED = true serves a batch with at least one biased item: thr_lds is the byte offset of
 // the LDS thresholds, 0 when the batch reads them from g_thr (item i's at 32 * a_at, zero-padded).
-template <bool BIASED>
+// TRACK (best-assignment tracking): a pass that finds strictly fewer violated clauses
+// than every pass before it copies the assignment it evaluated (s_A, untouched since the eval) to the
+// item's words of g_best, before the solved and the capped break; the record's two numbers travel in
+// SmallState from launch to launch.  The LDS layout is the untracked one.
+template <bool BIASED, bool TRACK = false>
 __device__ __forceinline__ void small_body(const SmallItem* __restrict__ items, SmallState* __restrict__ states,
                                                 const uint16_t* __restrict__ g_lits,
                                                 const uint16_t* __restrict__ g_offs, uint32_t* __restrict__ g_A,
                                                 const SmallLds& L, const uint32_t slice,
                                                 const uint32_t serial_max, const uint32_t* __restrict__ g_thr,
-                                                const uint32_t thr_lds) {
+                                                const uint32_t thr_lds, uint32_t* __restrict__ g_best = nullptr) {
     extern __shared__ __align__(16) unsigned char smem[];
     const SmallItem it = items[blockIdx.x];
     SmallState st = states[blockIdx.x];
@@ -160,6 +164,11 @@ __device__ __forceinline__ void small_body(const SmallItem* __restrict__ items, 
         }
         __syncthreads();
         u = s_prefix[groups];
+        if (TRACK && u < st.best_u) {  // (uniform: every thread holds the state)
+            st.best_u = u;
+            st.best_iter = n_iter;
+            for (uint32_t w = tid; w < it.n_words; w += nt) g_best[it.a_at + w] = s_A[w];
+        }
         if (u == 0) { done = 1; break; }                     // solved (check_if_noUNSAT)
         if (n_iter >= st.limit_nores) { done = 2; break; }   // the capped pass does not resample
 
@@ -273,6 +282,26 @@ __global__ void __launch_bounds__(1024) k_small_biased(const SmallItem* __restri
     small_body<true>(items, states, g_lits, g_offs, g_A, L, slice, serial_max, g_thr, thr_lds);
 }
 
+// ... with best-assignment tracking
+__global__ void __launch_bounds__(1024) k_small_best(const SmallItem* __restrict__ items, SmallState* __restrict__ states,
+                                                     const uint16_t* __restrict__ g_lits,
+                                                     const uint16_t* __restrict__ g_offs, uint32_t* __restrict__ g_A,
+                                                     const SmallLds L, const uint32_t slice, const uint32_t serial_max,
+                                                     uint32_t* __restrict__ g_best) {
+    small_body<false, true>(items, states, g_lits, g_offs, g_A, L, slice, serial_max, nullptr, 0u, g_best);
+}
+
+__global__ void __launch_bounds__(1024) k_small_biased_best(const SmallItem* __restrict__ items,
+                                                            SmallState* __restrict__ states,
+                                                            const uint16_t* __restrict__ g_lits,
+                                                            const uint16_t* __restrict__ g_offs,
+                                                            uint32_t* __restrict__ g_A, const SmallLds L,
+                                                            const uint32_t slice, const uint32_t serial_max,
+                                                            const uint32_t* __restrict__ g_thr, const uint32_t thr_lds,
+                                                            uint32_t* __restrict__ g_best) {
+    small_body<true, true>(items, states, g_lits, g_offs, g_A, L, slice, serial_max, g_thr, thr_lds, g_best);
+}
+
 __global__ void k_small_init(const SmallItem* __restrict__ items, uint32_t* __restrict__ g_A) {
     const SmallItem it = items[blockIdx.x];
     for (uint32_t w = threadIdx.x; w < it.n_words; w += blockDim.x) {
@@ -303,7 +332,12 @@ hipError_t small_prepare() {
     const SmallLds top = small_lds_layout(ALLL_BATCH_MAX_VARS, ALLL_BATCH_MAX_CLAUSES, ALLL_BATCH_MAX_LITERALS);
     hipError_t e = hipFuncSetAttribute((const void*)k_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)top.bytes);
     if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)k_small_best, hipFuncAttributeMaxDynamicSharedMemorySize, (int)top.bytes);
+    if (e != hipSuccess) return e;
     // (with LDS thresholds a layout goes up to the budget; beyond it the batch reads them from global memory)
+    e = hipFuncSetAttribute((const void*)k_small_biased_best, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)SMALL_LDS_BUDGET);
+    if (e != hipSuccess) return e;
     return hipFuncSetAttribute((const void*)k_small_biased, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)SMALL_LDS_BUDGET);
 }
@@ -320,6 +354,17 @@ hipError_t launch_small_limits(const SmallBatch& b, bool solve, uint64_t value, 
 }
 
 hipError_t launch_small_slice(const SmallBatch& b, uint32_t slice, hipStream_t s) {
+    if (b.best) {  // best-assignment tracking: the same choice among the tracked instantiations
+        if (b.biased) {
+            const uint32_t bytes = b.thr_lds ? b.lds_thr_bytes : b.lds.bytes;
+            hipLaunchKernelGGL(k_small_biased_best, dim3(b.n_items), dim3(b.threads), bytes, s, b.items, b.states,
+                               b.lits, b.offs, b.A, b.lds, slice, b.serial_max, b.thr, b.thr_lds, b.best);
+            return hipGetLastError();
+        }
+        hipLaunchKernelGGL(k_small_best, dim3(b.n_items), dim3(b.threads), b.lds.bytes, s, b.items, b.states, b.lits,
+                           b.offs, b.A, b.lds, slice, b.serial_max, b.best);
+        return hipGetLastError();
+    }
     if (b.biased) {  // at least one item has thresholds
         const uint32_t bytes = b.thr_lds ? b.lds_thr_bytes : b.lds.bytes;
         hipLaunchKernelGGL(k_small_biased, dim3(b.n_items), dim3(b.threads), bytes, s, b.items, b.states, b.lits,

@@ -133,12 +133,14 @@ def pinned_conflict(n_vars: int, offsets, literals, thr) -> Optional[int]:
 # ----------------------------------------------------------------------------- Solver
 class Solver:
     """Owns one device solver context (alll_ctx).  probabilities: P(x_v = 1) per variable (0 and 1
-    pin the variable; set_probabilities), None = fair coins, the unbiased stream."""
+    pin the variable; set_probabilities), None = fair coins, the unbiased stream.  track_best: keep
+    the best assignment the loop evaluates (track_best, best)."""
 
     def __init__(self, n_vars: int, offsets, literals, seed: int = 1, max_iters: int = 0,
                  device: int = -1, n_threads: int = 1, rank: int = 0, world: int = 1,
                  comm_id: Optional[bytes] = None, flags: int = 0, grid_rounds: int = 0,
-                 exchange=None, stream_batch: int = 0, set_starts=None, probabilities=None):
+                 exchange=None, stream_batch: int = 0, set_starts=None, probabilities=None,
+                 track_best: bool = False):
         self._L = N.lib()
         self.n_vars = int(n_vars)
         self.offsets = np.ascontiguousarray(offsets, np.uint64)
@@ -166,12 +168,29 @@ class Solver:
         self._xfn = None
         if exchange is not None:
             self.set_host_exchange(exchange)
-        if probabilities is not None:
-            try:
+        try:
+            if probabilities is not None:
                 self.set_probabilities(probabilities)
-            except Exception:
-                self.close()
-                raise
+            if track_best:
+                self.track_best()
+        except Exception:
+            self.close()
+            raise
+
+    def track_best(self, on: bool = True):
+        """alll_track_best: keep (or stop keeping) the best assignment the loop's eval passes see.
+        Before the first iteration only (alll.h)."""
+        N.check(self._L.alll_track_best(self._ctx, 1 if on else 0), "alll_track_best")
+
+    def best(self) -> dict:
+        """alll_get_best: {"n_violated", "iteration", "words"} of the first eval pass with the fewest
+        violated clauses: the assignment it evaluated, bit-packed.  Before any pass: n_violated
+        2^64 - 1, iteration 0, words all zero."""
+        nv, it = ctypes.c_uint64(), ctypes.c_uint64()
+        w = np.zeros((self.n_vars + 31) // 32, np.uint32)
+        N.check(self._L.alll_get_best(self._ctx, ctypes.byref(nv), ctypes.byref(it), _p(w, _u32p), w.size),
+                "alll_get_best")
+        return {"n_violated": int(nv.value), "iteration": int(it.value), "words": w}
 
     def set_probabilities(self, p):
         """P(x_v = 1) per variable (n_vars entries; 0 and 1 pin the variable), or None for the
@@ -460,6 +479,20 @@ class _ItemSolver:
             return
         thr = np.ascontiguousarray(thr, np.uint32)
         N.check(self._fn("set_var_thresholds")(self._h, i, _p(thr, _u32p), thr.size), f"{self._KIND} set_var_thresholds")
+
+    def track_best(self, on: bool = True):
+        """Solver.track_best for every item at once; before the first iteration only."""
+        N.check(self._fn("track_best")(self._h, 1 if on else 0), f"alll_{self._KIND}_track_best")
+
+    def best(self, i: int) -> dict:
+        """Solver.best of item i, in its own variable numbering and pass count.  The best of a
+        portfolio that does not solve: min(range(n), key=lambda i: s.best(i)["n_violated"])."""
+        nv, it = ctypes.c_uint64(), ctypes.c_uint64()
+        n = self.n_vars[i] if 0 <= i < self.n_items else 0  # (an item out of range: the library refuses it)
+        w = np.zeros((n + 31) // 32, np.uint32)
+        N.check(self._fn("get_best")(self._h, i, ctypes.byref(nv), ctypes.byref(it), _p(w, _u32p), w.size),
+                f"alll_{self._KIND}_get_best")
+        return {"n_violated": int(nv.value), "iteration": int(it.value), "words": w}
 
 
 class BatchSolver(_ItemSolver):

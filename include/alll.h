@@ -220,6 +220,43 @@ int alll_set_assignment_words(alll_ctx* ctx, const uint32_t* in, uint64_t n_word
  * stream_batch != 0.  (No reference counterpart: the reference draws fair coins.) */
 int alll_set_var_thresholds(alll_ctx* ctx, const uint32_t* thr, uint64_t n);
 
+/* The best assignment seen: an anytime answer for runs that end at max_iters.
+ * Opt-in, off by default.  While it is on, the device keeps a record of the best eval pass of the
+ * loop:
+ *   n_violated  the smallest number of violated clauses any eval pass has found;
+ *   iteration   the n_iterations value of the first pass that found it (the comparison is a strict
+ *               `<`: a later pass that ties the minimum does not replace the record);
+ *   words       the assignment that pass evaluated, ceil(n_vars/32) words: the assignment before
+ *               that pass's resample.
+ * Contract:
+ *  - Before any pass has run, iteration == 0, n_violated == UINT64_MAX and `words` is left untouched.
+ *  - Only passes of the loop count (alll_solve, alll_run and their batch and group forms);
+ *    alll_verify, alll_bench_eval and alll_profile's standalone counts never touch the record.
+ *  - The solved pass (no violated clause) and the capped pass (the max_iters-th pass of alll_solve,
+ *    which does not resample) are passes like any other: if one is the strict minimum, it is the
+ *    record.
+ *  - A later alll_run lifts the cap and continues the loop; the record survives the continuation
+ *    unchanged until a pass beats it.  run(a) then run(b) gives the record of run(a + b), and
+ *    alll_solve in several calls that of one call.
+ *  - alll_set_assignment* does not touch the record: the next pass evaluates the new assignment and
+ *    replaces the record only if it is strictly better.
+ *  - alll_set_var_thresholds and alll_track_best may come in either order while n_iterations == 0
+ *    (the record is still empty); the record obeys pins, being an assignment the loop produced.
+ *  - Nothing else changes: trajectory, statistics, MIS and violated mask of a tracking context are
+ *    bit for bit those of one that does not track.
+ * alll_track_best(on != 0 / 0) is allowed only while no iteration has run (the loop's kernels take
+ * their buffers by value and captured iterations keep them): afterwards ALLL_ERR_INVALID_ARG, and
+ * nothing changes.  It refuses the contexts alll_set_var_thresholds refuses, with
+ * ALLL_ERR_UNSUPPORTED before any device work (the message names the reason): ALLL_FLAG_REFERENCE_RNG,
+ * ALLL_FLAG_EXCHANGE_ALLREDUCE, world != 1 or a non-zero comm_id, stream_batch != 0.  Supported: any
+ * n_threads, ALLL_FLAG_LFMIS and every flag that does not change results.
+ * alll_get_best drains the stream; n_violated, iteration and words may each be NULL; n_words must be
+ * ceil(n_vars/32) when words is given.  A null handle, a wrong n_words, or a context that does not
+ * track (the message says so): ALLL_ERR_INVALID_ARG.  (No reference counterpart: the reference
+ * returns the last assignment.) */
+int alll_track_best(alll_ctx* ctx, int on);
+int alll_get_best(alll_ctx* ctx, uint64_t* n_violated, uint64_t* iteration, uint32_t* words, uint64_t n_words);
+
 /* Introspection of the last iteration (parity tests): violated bitmask of the last eval
  * pass (ceil(n_clauses/64) words) and the MIS picked from it (ascending clause order). */
 int alll_get_violated_mask(alll_ctx* ctx, uint64_t* out, uint64_t n_words);
@@ -325,6 +362,14 @@ int alll_batch_set_slice(alll_batch* b, uint64_t iters_per_launch);
  * ALLL_BATCH_FIRST_SOLVED, items that are one instance under different pinned variables make a cube
  * portfolio (alll_pinned_conflict drops the cubes that cannot be met). */
 int alll_batch_set_var_thresholds(alll_batch* b, uint64_t item, const uint32_t* thr, uint64_t n);
+/* alll_track_best / alll_get_best per item (the contract above): switched for every
+ * item at once, while no item has made an iteration (else ALLL_ERR_INVALID_ARG); every item keeps
+ * its own record, in its own pass count, exactly that of a tracking context created from it.  The
+ * records survive the slice boundaries and ALLL_BATCH_FIRST_SOLVED returns.  A null batch,
+ * item >= n_items, a wrong n_words or a batch that does not track: ALLL_ERR_INVALID_ARG. */
+int alll_batch_track_best(alll_batch* b, int on);
+int alll_batch_get_best(alll_batch* b, uint64_t item, uint64_t* n_violated, uint64_t* iteration, uint32_t* words,
+                        uint64_t n_words);
 
 /* ---- block-diagonal groups: many instances of any size at once -------
  * The items are laid side by side as one instance with disjoint variable and clause ranges, and
@@ -377,6 +422,16 @@ int alll_group_set_assignment_words(alll_group* g, uint64_t item, const uint32_t
  * ALLL_GROUP_FIRST_SOLVED, items that are one instance under different pinned variables make a
  * cube portfolio: the first cube solved wins. */
 int alll_group_set_var_thresholds(alll_group* g, uint64_t item, const uint32_t* thr, uint64_t n);
+/* alll_track_best / alll_get_best per item (the contract above): switched for every
+ * item at once, before the group's first iteration; the same ALLL_ERR_UNSUPPORTED contexts.  Every
+ * item keeps its own record, in its local variable numbering and its own pass count, exactly that
+ * of a tracking context created from it.  A solved item's record is its final assignment with
+ * n_violated = 0 and iteration = its n_iterations; it never changes afterwards, whatever the other
+ * items run.  A null group, item >= n_items, a wrong n_words or a group that does not track:
+ * ALLL_ERR_INVALID_ARG. */
+int alll_group_track_best(alll_group* g, int on);
+int alll_group_get_best(alll_group* g, uint64_t item, uint64_t* n_violated, uint64_t* iteration, uint32_t* words,
+                        uint64_t n_words);
 /* alll_layout / alll_eval_kernel of the union. */
 int alll_group_layout(alll_group* g);
 const char* alll_group_eval_kernel(alll_group* g);
