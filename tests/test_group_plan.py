@@ -118,6 +118,38 @@ def test_union_layout_matches_the_numpy_restatement(plan):
     assert i33["n_words"] == 2 and w[4 * (i33["word_base"] + 1) + 3] == 1  # n_vars = 33: one variable in the last word
 
 
+@pytest.mark.parametrize("fixed", [False, True], ids=["ragged", "fixed"])
+def test_swarm_plan_matches_the_numpy_restatement(plan, native, fixed):
+    """The thousand-item swarms of tests/swarm_cases.py: the clause bases with their runs of equal
+    entries (clauseless items at the front, in the middle and at the end), the seed's high word in
+    every word row, and the tail masks of one-word items."""
+    from swarm_cases import swarm
+
+    items, seeds = swarm(fixed=fixed)
+    r = plan(items, [(i, s) for i, s in enumerate(seeds)])
+    assert r["rc"] == OK
+    n_vars, offs, lits, places = compose(items)
+    assert r["shape"] == [n_vars, 24605, 1456]
+    bases = [pl["clause_base"] for pl in places] + [offs.size - 1]
+    assert r["clause_base"] == bases
+    assert bases[:4] == [0, 0, 0, 0] and len(set(bases[300:342])) == 1 and len(set(bases[342:381])) == 1
+    assert bases[-71:] == [24605] * 71 and bases[-72] < 24605
+    for it, pl, s in zip(r["item"], places, seeds):
+        assert it == [s, pl["lit_base"], pl["n_vars"], pl["n_words"], pl["var_base"], pl["word_base"], pl["clause_base"],
+                      pl["n_clauses"]]
+    w = r["words"]
+    rows = [tuple(w[4 * i:4 * i + 4]) for i in range(len(w) // 4)]
+    want = word_table(items, seeds)
+    assert rows == want
+    assert all(row[1] == seeds[i] >> 32 for i, pl in enumerate(places)
+               for row in rows[pl["word_base"]:pl["word_base"] + pl["n_words"]])
+    assert len({row[1] for row in rows}) == len(items) and {row[0] for row in rows} == {0, 1, 2, 3, 4}
+    tails = {rows[pl["word_base"] + pl["n_words"] - 1][3] for pl in places}
+    assert {0x7FFFFFFF, 0xFFFFFFFF, 1, 0x7F, 0xFFFFFF} <= tails  # n = 31, 32, 33 and 65, 7, 120
+    assert r["offsets"] == [int(x) for x in offs]
+    assert r["literals"] == [int(x) for x in lits]
+
+
 def test_item_errors_name_the_item(plan):
     good = ksat(50, 20, 3, 4)
     n, offs, lits = good
