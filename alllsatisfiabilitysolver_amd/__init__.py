@@ -4,9 +4,9 @@ The hot path -- clause evaluation, violated-clause compaction, exact lexicograph
 MIS and Philox resampling -- runs in hand-written gfx950 HIP kernels behind the C-ABI of
 include/alll.h (liballl.so).  This package is the Python front-end of that library.
 """
-from ._native import AlllError, build, lib  # noqa: F401
+from ._native import (AlllError, PROP_CONFLICT, PROP_FIXPOINT, PROP_NONE, PROP_ROUND_CAP, build, lib)  # noqa: F401
 from .solver import (BatchSolver, Clause, GroupSolver, SATInstance, Solver, Statistics, VariablesArray,  # noqa: F401
-                     batch_fits, solve_portfolio, solve_cubes, cube_thresholds, pinned_conflict, var_thresholds,
+                     batch_fits, solve_portfolio, solve_cubes, solve_cubes_propagated, cube_thresholds, pinned_conflict, propagate_pins, var_thresholds,
                      biased_initial_assignment,
                      assignment_digest, comm_unique_id, device_count, generate_ksat, generate_mixed, gloo_exchange,
                      parse_dimacs,

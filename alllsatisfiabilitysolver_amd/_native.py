@@ -46,6 +46,11 @@ BATCH_MAX_SLICE = 65536
 BATCH_FIRST_SOLVED = 1 << 0
 # block-diagonal groups (alll_group_*)
 GROUP_FIRST_SOLVED = 1 << 0
+# unit propagation of the pinned variables (alll_propagate_result.status)
+PROP_FIXPOINT = 0
+PROP_CONFLICT = 1
+PROP_ROUND_CAP = 2
+PROP_NONE = 3
 
 # Every symbol include/alll.h declares (checked by tests/test_abi.py).
 EXPORTED = [
@@ -65,6 +70,9 @@ EXPORTED = [
     "alll_group_set_var_thresholds", "alll_batch_set_var_thresholds", "alll_pinned_conflict",
     "alll_track_best", "alll_get_best", "alll_group_track_best", "alll_group_get_best",
     "alll_batch_track_best", "alll_batch_get_best",
+    "alll_pinned_propagate", "alll_propagate_pins", "alll_get_var_thresholds",
+    "alll_group_propagate_pins", "alll_group_get_var_thresholds",
+    "alll_batch_propagate_pins", "alll_batch_get_var_thresholds",
 ]
 
 
@@ -132,6 +140,18 @@ class PhaseTimes(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PropagateResult(ctypes.Structure):
+    _fields_ = [
+        ("conflict_clause", ctypes.c_uint64),
+        ("n_forced", ctypes.c_uint64),
+        ("rounds", ctypes.c_uint32),
+        ("status", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -215,6 +235,14 @@ _SIGS = {
     "alll_group_get_best": ([_vp, ctypes.c_uint64, _u64p, _u64p, _u32p, ctypes.c_uint64], ctypes.c_int),
     "alll_batch_track_best": ([_vp, ctypes.c_int], ctypes.c_int),
     "alll_batch_get_best": ([_vp, ctypes.c_uint64, _u64p, _u64p, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_pinned_propagate": ([ctypes.POINTER(Problem), _u32p, ctypes.c_uint64, ctypes.c_uint64,
+                               ctypes.POINTER(PropagateResult)], ctypes.c_int),
+    "alll_propagate_pins": ([_vp, ctypes.c_uint64, ctypes.POINTER(PropagateResult)], ctypes.c_int),
+    "alll_get_var_thresholds": ([_vp, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_group_propagate_pins": ([_vp, ctypes.c_uint64, ctypes.POINTER(PropagateResult)], ctypes.c_int),
+    "alll_group_get_var_thresholds": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_batch_propagate_pins": ([_vp, ctypes.c_uint64, ctypes.POINTER(PropagateResult)], ctypes.c_int),
+    "alll_batch_get_var_thresholds": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
 }
 
 _lib = None

@@ -326,6 +326,64 @@ int alll_batch_set_var_thresholds(alll_batch* b, uint64_t item, const uint32_t* 
     return ALLL_OK;
 }
 
+// Unit propagation of every item's pins: one launch, a workgroup per item; then the
+// propagated items' words again, as alll_batch_set_var_thresholds writes them.
+int alll_batch_propagate_pins(alll_batch* b, uint64_t max_rounds, alll_propagate_result* results) {
+    if (!b || !results) return fail(ALLL_ERR_INVALID_ARG, "propagate pins: null argument");
+    HIP_TRY(hipSetDevice(b->device));
+    if (int rc = read_states(b)) return rc;  // (drains the stream)
+    const uint32_t n = b->d.n_items;
+    for (uint32_t i = 0; i < n; ++i)
+        if (b->h_state[i].n_iter != 0)
+            return fail(ALLL_ERR_INVALID_ARG, "propagate pins: allowed before the batch's first iteration only "
+                                              "(item %u has made %llu)", i, (unsigned long long)b->h_state[i].n_iter);
+    if (!b->d.thr) {  // no item has ever had thresholds
+        for (uint32_t i = 0; i < n; ++i) results[i] = alll_propagate_result{b->items[i].m, 0, 0, ALLL_PROP_NONE};
+        return ALLL_OK;
+    }
+    SmallProp* d_out = nullptr;
+    if (hipMalloc((void**)&d_out, sizeof(SmallProp) * n) != hipSuccess)
+        return fail(ALLL_ERR_OOM, "hipMalloc(%zu bytes) failed", sizeof(SmallProp) * n);
+    std::vector<SmallProp> out(n);
+    // (more rounds than an item has variables never apply: such a cap is no cap)
+    const uint32_t cap = max_rounds > ALLL_BATCH_MAX_VARS + 1u ? 0u : (uint32_t)max_rounds;
+    hipError_t e = launch_small_propagate(b->d, const_cast<uint32_t*>(b->d.thr), cap, d_out, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, sizeof(SmallProp) * n, hipMemcpyDeviceToHost);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(ALLL_ERR_HIP, "propagate kernel failed: %s", hipGetErrorString(e));
+    std::vector<uint32_t> thr, w;
+    std::vector<uint8_t> bits;
+    for (uint32_t i = 0; i < n; ++i) {
+        const SmallItem& it = b->items[i];
+        results[i] = alll_propagate_result{out[i].conflict, out[i].n_forced, out[i].rounds, (int32_t)out[i].status};
+        if (out[i].status == ALLL_PROP_NONE || !it.n_words) continue;
+        thr.resize(it.n_vars);
+        bits.resize(it.n_vars);
+        HIP_TRY(hipMemcpy(thr.data(), b->d.thr + 32ull * it.a_at, (size_t)it.n_vars * 4, hipMemcpyDeviceToHost));
+        if (int rc = alll_biased_initial_assignment(it.seed, it.n_vars, thr.data(), bits.data())) return rc;
+        w.assign(it.n_words, 0u);
+        for (uint32_t v = 0; v < it.n_vars; ++v) w[v >> 5] |= (uint32_t)bits[v] << (v & 31);
+        HIP_TRY(hipMemcpy(b->d.A + it.a_at, w.data(), it.n_words * 4ull, hipMemcpyHostToDevice));
+    }
+    return ALLL_OK;
+}
+
+int alll_batch_get_var_thresholds(alll_batch* b, uint64_t item, uint32_t* out, uint64_t n) {
+    if (!b) return fail(ALLL_ERR_INVALID_ARG, "null batch");
+    if (item >= b->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, b->d.n_items);
+    const SmallItem& it = b->items[item];
+    if (!b->d.thr || !it.pad)
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: item %llu has none", (unsigned long long)item);
+    if (n != it.n_vars || (!out && n))
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: %llu entries for the %u variables of item %llu",
+                    (unsigned long long)n, it.n_vars, (unsigned long long)item);
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (n) HIP_TRY(hipMemcpy(out, b->d.thr + 32ull * it.a_at, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return ALLL_OK;
+}
+
 int alll_batch_track_best(alll_batch* b, int on) {
     if (!b) return fail(ALLL_ERR_INVALID_ARG, "null batch");
     HIP_TRY(hipSetDevice(b->device));

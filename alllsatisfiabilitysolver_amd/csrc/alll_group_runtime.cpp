@@ -14,6 +14,7 @@
 #include "alll.h"
 #include "alll_group.h"
 #include "alll_group_dev.h"
+#include "alll_propagate.h"
 #include "alll_rt_util.h"
 
 using namespace alll;
@@ -34,6 +35,7 @@ struct alll_group {
     const uint32_t* d_wbias = nullptr;
     std::vector<uint32_t> wbias;   // host copy
     std::vector<uint8_t> biased;   // per item
+    const uint32_t* d_word_item = nullptr;  // unit propagation: the item of every word of the union
     // best-assignment tracking, allocated at the first alll_group_track_best(on):
     // the items' records and flags and the item of every word (the context keeps a pointer to it)
     GroupBest best{};
@@ -284,6 +286,70 @@ int alll_group_set_var_thresholds(alll_group* g, uint64_t item, const uint32_t* 
         hipStreamSynchronize(g->stream) != hipSuccess)
         return fail(ALLL_ERR_HIP, "fill kernel failed: %s", hipGetErrorString(hipGetLastError()));
     ctx_assignment_changed(g->ctx);
+    return ALLL_OK;
+}
+
+// Unit propagation of every item's pins at once: the context's three kernels over the
+// union, the items' records apart; a global round is every unfinished item's own round.
+int alll_group_propagate_pins(alll_group* g, uint64_t max_rounds, alll_propagate_result* results) {
+    if (!g || !results) return fail(ALLL_ERR_INVALID_ARG, "propagate pins: null argument");
+    int rc;
+    if ((rc = ctx_bias_supported(g->ctx))) return rc;
+    HIP_TRY(hipSetDevice(g->device));
+    if ((rc = read_all(g))) return rc;  // (drains the stream)
+    const CtxAccess a = ctx_access(g->ctx);
+    if (a.h_state->n_iter != 0)
+        return fail(ALLL_ERR_INVALID_ARG, "propagate pins: allowed before the group's first iteration only (%llu made)",
+                    (unsigned long long)a.h_state->n_iter);
+    const uint32_t n = g->d.n_items;
+    std::vector<uint8_t> on(n, 0);
+    if (g->d_thr) on = g->biased;
+    if (g->d_thr && !g->d_word_item) {
+        std::vector<uint32_t> word_item(a.b->n_words, 0u);
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t w = 0; w < g->items[i].n_words; ++w) word_item[g->items[i].word_base + w] = i;
+        if ((rc = upload(g, &g->d_word_item, word_item.data(), word_item.size()))) return rc;
+    }
+    PropArgs p{};
+    p.lits = a.cv->lits;
+    p.offs = a.cv->offs;
+    p.m = a.cv->m;
+    p.k = a.cv->k;
+    p.n_vars = a.b->n_vars;
+    p.n_words = a.b->n_words;
+    p.n_items = n;
+    p.thr = const_cast<uint32_t*>(g->d_thr);
+    p.words = g->d.words;
+    p.wbias = g->d_wbias;
+    p.word_item = g->d_word_item;
+    p.clause_base = g->d.clause_base;
+    if ((rc = prop_drive(p, on.data(), max_rounds, results, g->stream))) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+        const GroupItem& it = g->items[i];
+        alll_propagate_result& r = results[i];
+        // the item's own clause index; its words again, the biased fill of its propagated thresholds
+        r.conflict_clause = r.status == ALLL_PROP_CONFLICT ? r.conflict_clause - it.clause_base : it.n_clauses;
+        if (on[i] && launch_fill_words(a.b->A + it.word_base, it.n_words, it.n_vars, g->d_thr + it.var_base, it.seed,
+                                       g->stream) != hipSuccess)
+            return fail(ALLL_ERR_HIP, "fill kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    ctx_assignment_changed(g->ctx);
+    return ALLL_OK;
+}
+
+int alll_group_get_var_thresholds(alll_group* g, uint64_t item, uint32_t* out, uint64_t n) {
+    if (!g) return fail(ALLL_ERR_INVALID_ARG, "null group");
+    if (item >= g->d.n_items) return fail(ALLL_ERR_INVALID_ARG, "item %llu of %u", (unsigned long long)item, g->d.n_items);
+    const GroupItem& it = g->items[item];
+    if (!g->d_thr || !g->biased[item])
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: item %llu has none", (unsigned long long)item);
+    if (n != it.n_vars || (!out && n))
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: %llu entries for the %u variables of item %llu",
+                    (unsigned long long)n, it.n_vars, (unsigned long long)item);
+    HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (n) HIP_TRY(hipMemcpy(out, g->d_thr + it.var_base, (size_t)n * 4, hipMemcpyDeviceToHost));
     return ALLL_OK;
 }
 

@@ -493,40 +493,48 @@ int alll_biased_initial_assignment(uint64_t seed, uint32_t n_vars, const uint32_
     return ALLL_OK;
 }
 
-int alll_pinned_conflict(const alll_problem* prob, const uint32_t* thr, uint64_t n, uint64_t* clause) {
-    if (!prob || !clause || (!thr && n)) {
-        g_host_err = "pinned conflict: null argument";
+// The validation alll_pinned_conflict and alll_pinned_propagate share (`what` opens the message).
+static int pinned_validate(const alll_problem* prob, const uint32_t* thr, uint64_t n, const void* out, const char* what) {
+    const std::string w(what);
+    if (!prob || !out || (!thr && n)) {
+        g_host_err = w + ": null argument";
         return ALLL_ERR_INVALID_ARG;
     }
     if (n != prob->n_vars) {
-        g_host_err = "pinned conflict: " + std::to_string(n) + " thresholds for " + std::to_string(prob->n_vars) + " variables";
+        g_host_err = w + ": " + std::to_string(n) + " thresholds for " + std::to_string(prob->n_vars) + " variables";
         return ALLL_ERR_INVALID_ARG;
     }
     const uint64_t m = prob->n_clauses;
     if (m && !prob->offsets) {
-        g_host_err = "pinned conflict: null offsets";
+        g_host_err = w + ": null offsets";
         return ALLL_ERR_INVALID_ARG;
     }
     if (m && prob->offsets[0] != 0) {
-        g_host_err = "pinned conflict: offsets[0] != 0";
+        g_host_err = w + ": offsets[0] != 0";
         return ALLL_ERR_BAD_INPUT;
     }
     for (uint64_t c = 0; c < m; ++c)
         if (prob->offsets[c + 1] < prob->offsets[c]) {
-            g_host_err = "pinned conflict: offsets decrease at " + std::to_string(c);
+            g_host_err = w + ": offsets decrease at " + std::to_string(c);
             return ALLL_ERR_BAD_INPUT;
         }
     const uint64_t L = m ? prob->offsets[m] : 0;
     if (L && !prob->literals) {
-        g_host_err = "pinned conflict: null literals";
+        g_host_err = w + ": null literals";
         return ALLL_ERR_INVALID_ARG;
     }
     for (uint64_t j = 0; j < L; ++j)
         if ((prob->literals[j] >> 1) >= prob->n_vars) {
-            g_host_err = "pinned conflict: literal " + std::to_string(prob->literals[j]) + " at position " +
-                         std::to_string(j) + " exceeds n_vars " + std::to_string(prob->n_vars);
+            g_host_err = w + ": literal " + std::to_string(prob->literals[j]) + " at position " + std::to_string(j) +
+                         " exceeds n_vars " + std::to_string(prob->n_vars);
             return ALLL_ERR_LITERAL_RANGE;
         }
+    return ALLL_OK;
+}
+
+int alll_pinned_conflict(const alll_problem* prob, const uint32_t* thr, uint64_t n, uint64_t* clause) {
+    if (int rc = pinned_validate(prob, thr, n, clause, "pinned conflict")) return rc;
+    const uint64_t m = prob->n_clauses;
     uint64_t first = m;
     for (uint64_t c = 0; c < m && first == m; ++c) {
         bool dead = true;
@@ -537,6 +545,60 @@ int alll_pinned_conflict(const alll_problem* prob, const uint32_t* thr, uint64_t
         if (dead) first = c;
     }
     *clause = first;
+    return ALLL_OK;
+}
+
+// Unit propagation of the pins (include/alll.h): rounds over all clauses, every clause judged against
+// the thresholds of the round's start, the forced literals applied at once.
+int alll_pinned_propagate(const alll_problem* prob, uint32_t* thr, uint64_t n, uint64_t max_rounds,
+                          alll_propagate_result* res) {
+    if (int rc = pinned_validate(prob, thr, n, res, "pinned propagate")) return rc;
+    const uint64_t m = prob->n_clauses;
+    const uint32_t nv = prob->n_vars;
+    std::vector<uint8_t> force(nv, 0);  // bit 0: forced to 1, bit 1: forced to 0
+    std::vector<uint32_t> touched;
+    alll_propagate_result r{m, 0, 0, ALLL_PROP_FIXPOINT};
+    for (;;) {
+        uint64_t conflict = m;
+        touched.clear();
+        for (uint64_t c = 0; c < m && conflict == m; ++c) {
+            bool sat = false;
+            uint32_t n_free = 0, unit = 0;
+            bool same = true;
+            for (uint64_t j = prob->offsets[c]; j < prob->offsets[c + 1] && !sat; ++j) {
+                const uint32_t l = prob->literals[j], t = thr[l >> 1];
+                if (t == ((l & 1u) ? 0u : 0xFFFFFFFFu)) sat = true;
+                else if (t != ((l & 1u) ? 0xFFFFFFFFu : 0u)) {
+                    if (n_free++ == 0) unit = l;
+                    else same = same && l == unit;
+                }
+            }
+            if (sat) continue;
+            if (!n_free) conflict = c;
+            else if (same) {
+                if (!force[unit >> 1]) touched.push_back(unit >> 1);
+                force[unit >> 1] |= (unit & 1u) ? 2 : 1;
+            }
+        }
+        if (conflict != m) {
+            for (uint32_t v : touched) force[v] = 0;
+            r.conflict_clause = conflict;
+            r.status = ALLL_PROP_CONFLICT;
+            break;
+        }
+        if (touched.empty()) break;  // (fixpoint)
+        if (max_rounds && r.rounds >= max_rounds) {
+            r.status = ALLL_PROP_ROUND_CAP;
+            break;
+        }
+        for (uint32_t v : touched) {
+            thr[v] = (force[v] & 1) ? 0xFFFFFFFFu : 0u;
+            force[v] = 0;
+        }
+        r.n_forced += touched.size();
+        r.rounds += 1;
+    }
+    *res = r;
     return ALLL_OK;
 }
 

@@ -23,6 +23,7 @@
 #include "alll_group_dev.h"
 #include "alll_internal.h"
 #include "alll_layout.h"
+#include "alll_propagate.h"
 #include "alll_rt_util.h"
 
 using namespace alll;
@@ -1377,6 +1378,53 @@ int alll_set_var_thresholds(alll_ctx* c, const uint32_t* thr, uint64_t n) {
     HIP_TRY(launch_fill_words(b.A, b.n_words, b.n_vars, b.thr, b.seed, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     ctx_assignment_changed(c);
+    return ALLL_OK;
+}
+
+// Unit propagation of the pins: the rounds run on the context's own thresholds,
+// then the assignment is the biased fill of the propagated thresholds, as after alll_set_var_thresholds.
+int alll_propagate_pins(alll_ctx* c, uint64_t max_rounds, alll_propagate_result* res) {
+    if (!c || !res) return fail(ALLL_ERR_INVALID_ARG, "propagate pins: null argument");
+    if (c->grp) return fail(ALLL_ERR_INVALID_ARG, "propagate pins: the context belongs to a group "
+                                                  "(alll_group_propagate_pins)");
+    int rc;
+    if ((rc = bias_supported(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = read_state(c))) return rc;  // (drains the stream)
+    if (c->h_state->n_iter != 0)
+        return fail(ALLL_ERR_INVALID_ARG, "propagate pins: allowed before the first iteration only (%llu made)",
+                    (unsigned long long)c->h_state->n_iter);
+    LoopBuffers& b = c->b;
+    if (!b.thr || !c->d_thr)
+        return fail(ALLL_ERR_INVALID_ARG, "propagate pins: the context has no thresholds (alll_set_var_thresholds first)");
+    PropArgs a{};
+    a.lits = c->cv.lits;
+    a.offs = c->cv.offs;
+    a.m = c->cv.m;
+    a.k = c->cv.k;
+    a.n_vars = b.n_vars;
+    a.n_words = b.n_words;
+    a.n_items = 1;
+    a.thr = c->d_thr;
+    const uint8_t on = 1;
+    if ((rc = prop_drive(a, &on, max_rounds, res, c->stream))) return rc;
+    HIP_TRY(launch_fill_words(b.A, b.n_words, b.n_vars, b.thr, b.seed, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    ctx_assignment_changed(c);
+    return ALLL_OK;
+}
+
+int alll_get_var_thresholds(alll_ctx* c, uint32_t* out, uint64_t n) {
+    if (!c || (!out && n)) return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: null argument");
+    if (c->grp) return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: the context belongs to a group "
+                                                  "(alll_group_get_var_thresholds)");
+    if (!c->b.thr || !c->d_thr) return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: the context has none");
+    if (n != c->n_vars)
+        return fail(ALLL_ERR_INVALID_ARG, "variable thresholds: %llu entries for %u variables", (unsigned long long)n,
+                    c->n_vars);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n) HIP_TRY(hipMemcpy(out, c->d_thr, (size_t)n * 4, hipMemcpyDeviceToHost));
     return ALLL_OK;
 }
 

@@ -28,6 +28,14 @@ struct SmallBatch {
     uint32_t* best;
 };
 
+// what k_small_propagate leaves per item
+struct SmallProp {
+    uint32_t conflict;  // smallest falsified clause, the item's m when there is none
+    uint32_t n_forced;
+    uint32_t rounds;
+    uint32_t status;    // ALLL_PROP_*
+};
+
 // the dynamic LDS attribute of both instantiations of the kernel (on the batch's device, before its first slice)
 hipError_t small_prepare();
 // initial assignment of every item: word w = Philox(seed, {w, 0, 0xFFFFFFFF, 0}).x, tail cleared
@@ -37,5 +45,8 @@ hipError_t launch_small_init(const SmallBatch& b, hipStream_t s);
 hipError_t launch_small_limits(const SmallBatch& b, bool solve, uint64_t value, hipStream_t s);
 // one slice: every unfinished item runs at most `slice` iterations (b.biased: the instantiation with thresholds)
 hipError_t launch_small_slice(const SmallBatch& b, uint32_t slice, hipStream_t s);
+// unit propagation of the pins of every item that has thresholds (pad != 0), all rounds in one launch;
+// thr: the threshold pool (b.thr, written); max_rounds 0: until a fixpoint or a conflict; out: n_items
+hipError_t launch_small_propagate(const SmallBatch& b, uint32_t* thr, uint32_t max_rounds, SmallProp* out, hipStream_t s);
 
 }  // namespace alll

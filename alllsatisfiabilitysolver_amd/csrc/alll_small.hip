@@ -311,6 +311,91 @@ __global__ void k_small_init(const SmallItem* __restrict__ items, uint32_t* __re
     }
 }
 
+// Unit propagation of the item's pins, a workgroup per item, all rounds in one
+// launch.  A round: every lane judges clauses (from the 16-bit pools) against the item's thresholds in
+// the pool as the last round left them; a falsified clause lowers s_conf, a unit sets its variable's
+// bit in s_F1 or s_F0 (LDS atomics: min and or do not depend on the order); after the barrier the
+// round ends the item (conflict, no unit, the cap) or the lanes write the forced pins to the pool.
+// Barriers only; the loop is bounded by max_rounds, or by n_vars + 1 rounds (a round that applies
+// pins at least one more variable).  Items without thresholds (pad == 0) are left alone.
+__global__ __launch_bounds__(256) void k_small_propagate(const SmallItem* __restrict__ items,
+                                                         const uint16_t* __restrict__ g_lits,
+                                                         const uint16_t* __restrict__ g_offs, uint32_t* g_thr,
+                                                         const uint32_t max_rounds, SmallProp* __restrict__ out) {
+    __shared__ uint32_t s_F1[ALLL_BATCH_MAX_VARS / 32], s_F0[ALLL_BATCH_MAX_VARS / 32];
+    __shared__ uint32_t s_conf, s_forced;
+    const SmallItem it = items[blockIdx.x];
+    const uint32_t tid = threadIdx.x, nt = blockDim.x;
+    if (it.pad == 0) {
+        if (tid == 0) out[blockIdx.x] = SmallProp{it.m, 0u, 0u, (uint32_t)ALLL_PROP_NONE};
+        return;
+    }
+    const uint16_t* lits = g_lits + it.lits_at;
+    const uint16_t* offs = g_offs + it.offs_at;
+    uint32_t* thr = g_thr + 32ull * it.a_at;
+    for (uint32_t w = tid; w < it.n_words; w += nt) s_F1[w] = s_F0[w] = 0;
+    if (tid == 0) {
+        s_conf = it.m;
+        s_forced = 0;
+    }
+    __syncthreads();
+    const uint32_t bound = max_rounds ? max_rounds : it.n_vars + 1u;
+    uint32_t rounds = 0, n_forced = 0, status = ALLL_PROP_FIXPOINT, conflict = it.m;
+    for (uint32_t round = 0; round <= bound; ++round) {
+        for (uint32_t c = tid; c < it.m; c += nt) {
+            bool sat = false, same = true;
+            uint32_t n_free = 0, unit = 0;
+            for (uint32_t j = offs[c]; j < offs[c + 1]; ++j) {
+                const uint32_t l = lits[j], t = thr[l >> 1];
+                if (t == ((l & 1u) ? 0u : 0xFFFFFFFFu)) {  // a true literal
+                    sat = true;
+                    break;
+                }
+                if (t == ((l & 1u) ? 0xFFFFFFFFu : 0u)) continue;
+                if (n_free++ == 0) unit = l;
+                else same = same && l == unit;
+            }
+            if (sat || (n_free && !same)) continue;
+            if (n_free == 0) atomicMin(&s_conf, c);
+            else atomicOr(((unit & 1u) ? s_F0 : s_F1) + (unit >> 6), 1u << ((unit >> 1) & 31u));
+        }
+        __syncthreads();
+        conflict = s_conf;
+        if (conflict == it.m) {  // (uniform: every lane reads the same word)
+            uint32_t cnt = 0;
+            for (uint32_t w = tid; w < it.n_words; w += nt) cnt += __popc(s_F1[w] | s_F0[w]);
+            for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d);
+            if ((tid & 63u) == 0 && cnt) atomicAdd(&s_forced, cnt);
+        }
+        __syncthreads();
+        const uint32_t forced = s_forced;
+        if (conflict != it.m) {
+            status = ALLL_PROP_CONFLICT;
+            break;
+        }
+        if (forced == 0) break;  // (fixpoint)
+        if (round >= bound) {
+            status = ALLL_PROP_ROUND_CAP;
+            break;
+        }
+        // apply: every unit's variable was free at the round's start (forced both ways: pinned to 1)
+        for (uint32_t w = tid; w < it.n_words; w += nt) {
+            const uint32_t f1 = s_F1[w], f0 = s_F0[w];
+            for (uint32_t r = f1 | f0; r; r &= r - 1u) {
+                const uint32_t bit = __ffs(r) - 1u;
+                thr[32u * w + bit] = ((f1 >> bit) & 1u) ? 0xFFFFFFFFu : 0u;
+            }
+            s_F1[w] = s_F0[w] = 0;
+        }
+        rounds += 1;
+        n_forced += forced;
+        __syncthreads();  // (orders the pool's new pins before the next round's loads, within the workgroup)
+        if (tid == 0) s_forced = 0;
+        __syncthreads();
+    }
+    if (tid == 0) out[blockIdx.x] = SmallProp{conflict, n_forced, rounds, status};
+}
+
 __global__ void k_small_limits(SmallState* __restrict__ states, uint32_t n_items, int solve, uint64_t value) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_items) return;
@@ -373,6 +458,12 @@ hipError_t launch_small_slice(const SmallBatch& b, uint32_t slice, hipStream_t s
     }
     hipLaunchKernelGGL(k_small, dim3(b.n_items), dim3(b.threads), b.lds.bytes, s, b.items, b.states, b.lits, b.offs,
                        b.A, b.lds, slice, b.serial_max);
+    return hipGetLastError();
+}
+
+hipError_t launch_small_propagate(const SmallBatch& b, uint32_t* thr, uint32_t max_rounds, SmallProp* out,
+                                  hipStream_t s) {
+    hipLaunchKernelGGL(k_small_propagate, dim3(b.n_items), dim3(256), 0, s, b.items, b.lits, b.offs, thr, max_rounds, out);
     return hipGetLastError();
 }
 

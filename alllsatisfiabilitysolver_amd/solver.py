@@ -130,6 +130,22 @@ def pinned_conflict(n_vars: int, offsets, literals, thr) -> Optional[int]:
     return None if c.value == m else int(c.value)
 
 
+def propagate_pins(n_vars: int, offsets, literals, thr, max_rounds: int = 0):
+    """alll_pinned_propagate: unit propagation of the pins of thresholds thr (host-only; the rounds of
+    include/alll.h).  Returns (propagated thresholds, {"status", "rounds", "n_forced",
+    "conflict_clause"}); status is one of PROP_FIXPOINT / PROP_CONFLICT / PROP_ROUND_CAP, conflict_clause
+    the number of clauses when there is none.  thr itself is left alone."""
+    offs = np.ascontiguousarray(offsets, np.uint64)
+    lits = np.ascontiguousarray(literals, np.uint32)
+    out = np.array(thr, np.uint32)  # (a copy: the library propagates in place)
+    m = max(0, offs.size - 1)
+    prob = N.Problem(int(n_vars), 0, m, _p(offs, _u64p), _p(lits, _u32p))
+    res = N.PropagateResult()
+    N.check(N.lib().alll_pinned_propagate(ctypes.byref(prob), _p(out, _u32p), out.size, max_rounds, ctypes.byref(res)),
+            "pinned_propagate")
+    return out, res.as_dict()
+
+
 # ----------------------------------------------------------------------------- Solver
 class Solver:
     """Owns one device solver context (alll_ctx).  probabilities: P(x_v = 1) per variable (0 and 1
@@ -204,6 +220,22 @@ class Solver:
             return
         thr = np.ascontiguousarray(thr, np.uint32)
         N.check(self._L.alll_set_var_thresholds(self._ctx, _p(thr, _u32p), thr.size), "set_var_thresholds")
+
+    def propagate_pins(self, max_rounds: int = 0) -> dict:
+        """alll_propagate_pins: unit propagation of the pinned variables on the device (max_rounds 0:
+        to the fixpoint or the conflict).  Before the first iteration, on a solver that has
+        thresholds; afterwards the solver is one given thresholds() from the start.  Returns
+        {"status", "rounds", "n_forced", "conflict_clause"} (propagate_pins, the host form)."""
+        res = N.PropagateResult()
+        N.check(self._L.alll_propagate_pins(self._ctx, max_rounds, ctypes.byref(res)), "alll_propagate_pins")
+        return res.as_dict()
+
+    def thresholds(self) -> np.ndarray:
+        """alll_get_var_thresholds: the solver's n_vars thresholds (the propagated ones after
+        propagate_pins)."""
+        thr = np.zeros(self.n_vars, np.uint32)
+        N.check(self._L.alll_get_var_thresholds(self._ctx, _p(thr, _u32p), thr.size), "alll_get_var_thresholds")
+        return thr
 
     def set_host_exchange(self, exchange):
         """exchange(op, buf: numpy uint8 view, bytes_per_rank_or_total) -> None; see
@@ -480,6 +512,21 @@ class _ItemSolver:
         thr = np.ascontiguousarray(thr, np.uint32)
         N.check(self._fn("set_var_thresholds")(self._h, i, _p(thr, _u32p), thr.size), f"{self._KIND} set_var_thresholds")
 
+    def propagate_pins(self, max_rounds: int = 0) -> List[dict]:
+        """Solver.propagate_pins for every item that has thresholds, at once; one dict per item, an
+        item without thresholds gets status PROP_NONE.  Before the first iteration only."""
+        res = (N.PropagateResult * max(1, self.n_items))()
+        N.check(self._fn("propagate_pins")(self._h, max_rounds, res), f"alll_{self._KIND}_propagate_pins")
+        return [res[i].as_dict() for i in range(self.n_items)]
+
+    def thresholds(self, i: int) -> np.ndarray:
+        """Solver.thresholds of item i."""
+        n = self.n_vars[i] if 0 <= i < self.n_items else 0  # (an item out of range: the library refuses it)
+        thr = np.zeros(n, np.uint32)
+        N.check(self._fn("get_var_thresholds")(self._h, i, _p(thr, _u32p), thr.size),
+                f"alll_{self._KIND}_get_var_thresholds")
+        return thr
+
     def track_best(self, on: bool = True):
         """Solver.track_best for every item at once; before the first iteration only."""
         N.check(self._fn("track_best")(self._h, 1 if on else 0), f"alll_{self._KIND}_track_best")
@@ -578,13 +625,26 @@ def cube_thresholds(n_vars: int, cube) -> np.ndarray:
     return thr
 
 
-def solve_cubes(n_vars: int, offsets, literals, cubes, seeds=None, max_iters: int = 0):
-    """A cube portfolio: one instance under every cube's pins (cube_thresholds) at once, the first
-    cube solved wins.  seeds: one per cube, default 1 .. len(cubes).  Cubes that pin every literal
-    of some clause false (pinned_conflict) are dropped on the host; the others run in a BatchSolver
-    when the instance fits one, else in a GroupSolver.  Returns (cube index, stats,
-    assignment_words) of the solved cube with the fewest iterations (on a tie the lowest index), or
-    (None, None, None) when no cube is left or max_iters capped every one."""
+def _run_cubes(cls, n_vars, offsets, literals, live, seeds, thrs, max_iters, propagate):
+    """One solver of solve_cubes over the cubes `live` under thrs[cube index].  -> (result, None); or,
+    when the propagation found cubes in conflict, (None, (the surviving cubes, their propagated
+    thresholds by cube index)): the caller builds a second solver from them."""
+    with cls([(n_vars, offsets, literals)] * len(live), [seeds[i] for i in live], max_iters=max_iters) as b:
+        for k, i in enumerate(live):
+            b.set_thresholds(k, thrs[i])
+        if propagate:
+            keep = [k for k, r in enumerate(b.propagate_pins()) if r["status"] != N.PROP_CONFLICT]
+            if len(keep) < len(live):
+                return None, ([live[k] for k in keep], {live[k]: b.thresholds(k) for k in keep})
+        res = b.solve(first_solved=True)
+        solved = [k for k, r in enumerate(res) if r["solved"]]
+        if not solved:
+            return (None, None, None), None
+        best = min(solved, key=lambda k: (res[k]["n_iterations"], k))
+        return (live[best], res[best], b.assignment_words(best)), None
+
+
+def _solve_cubes(n_vars, offsets, literals, cubes, seeds, max_iters, propagate):
     offsets = np.ascontiguousarray(offsets, np.uint64)
     literals = np.ascontiguousarray(literals, np.uint32)
     cubes = list(cubes)
@@ -597,15 +657,31 @@ def solve_cubes(n_vars: int, offsets, literals, cubes, seeds=None, max_iters: in
         return None, None, None
     fits = batch_fits(n_vars, max(0, offsets.size - 1), literals.size)
     cls = BatchSolver if fits else GroupSolver
-    with cls([(n_vars, offsets, literals)] * len(live), [seeds[i] for i in live], max_iters=max_iters) as b:
-        for k, i in enumerate(live):
-            b.set_thresholds(k, thrs[i])
-        res = b.solve(first_solved=True)
-        solved = [k for k, r in enumerate(res) if r["solved"]]
-        if not solved:
+    out, left = _run_cubes(cls, n_vars, offsets, literals, live, seeds, thrs, max_iters, propagate)
+    if left is not None:  # cubes conflicted: a second solver of the same kind from the survivors
+        live, thrs = left
+        if not live:
             return None, None, None
-        best = min(solved, key=lambda k: (res[k]["n_iterations"], k))
-        return live[best], res[best], b.assignment_words(best)
+        out, _ = _run_cubes(cls, n_vars, offsets, literals, live, seeds, thrs, max_iters, False)
+    return out
+
+
+def solve_cubes(n_vars: int, offsets, literals, cubes, seeds=None, max_iters: int = 0):
+    """A cube portfolio: one instance under every cube's pins (cube_thresholds) at once, the first
+    cube solved wins.  seeds: one per cube, default 1 .. len(cubes).  Cubes that pin every literal
+    of some clause false (pinned_conflict) are dropped on the host; the others run in a BatchSolver
+    when the instance fits one, else in a GroupSolver.  Returns (cube index, stats,
+    assignment_words) of the solved cube with the fewest iterations (on a tie the lowest index), or
+    (None, None, None) when no cube is left or max_iters capped every one."""
+    return _solve_cubes(n_vars, offsets, literals, cubes, seeds, max_iters, False)
+
+
+def solve_cubes_propagated(n_vars: int, offsets, literals, cubes, seeds=None, max_iters: int = 0):
+    """solve_cubes with unit propagation: the pins of the cubes left by the depth-0 filter are
+    propagated on the device first (propagate_pins); the cubes that turn out conflicting are dropped
+    as well, and the others run, in a second solver of the same kind, under their propagated
+    thresholds.  The return value is solve_cubes', the indices are the caller's."""
+    return _solve_cubes(n_vars, offsets, literals, cubes, seeds, max_iters, True)
 
 
 def shard_plan(n_clauses: int, world: int, rank: int):

@@ -214,7 +214,8 @@ int alll_set_assignment_words(alll_ctx* ctx, const uint32_t* in, uint64_t n_word
  * unbiased stream and the unbiased fill.  alll_set_assignment* afterwards is not checked against
  * the pins: a pinned variable keeps whatever value the caller gives it.  A clause whose literals
  * are all pinned false can never be satisfied: the loop then runs to max_iters (not detected on
- * the host).  Supported: any n_threads, every flag that does not change results, one GPU.
+ * the host; alll_propagate_pins below finds such clauses, also those the pins imply, before the
+ * loop starts).  Supported: any n_threads, every flag that does not change results, one GPU.
  * ALLL_ERR_UNSUPPORTED, before any device work (the message names the reason): a context created
  * with ALLL_FLAG_REFERENCE_RNG, ALLL_FLAG_EXCHANGE_ALLREDUCE, world != 1 or a non-zero comm_id, or
  * stream_batch != 0.  (No reference counterpart: the reference draws fair coins.) */
@@ -256,6 +257,48 @@ int alll_set_var_thresholds(alll_ctx* ctx, const uint32_t* thr, uint64_t n);
  * returns the last assignment.) */
 int alll_track_best(alll_ctx* ctx, int on);
 int alll_get_best(alll_ctx* ctx, uint64_t* n_violated, uint64_t* iteration, uint32_t* words, uint64_t n_words);
+
+/* Unit propagation of the pinned variables.  A literal l (variable v = l >> 1,
+ * negated when l & 1) is, under thresholds thr,
+ *   false  when thr[v] == (negated ? 0xFFFFFFFF : 0),
+ *   true   when thr[v] == (negated ? 0 : 0xFFFFFFFF),
+ *   free   otherwise (a bias that is not a pin is free).
+ * Propagation runs in rounds; every clause of a round is judged against the thresholds as they stood
+ * at the round's start:
+ *  1. a clause with a true literal is ignored;
+ *  2. a clause with no true and no free literal is falsified (an empty clause is): if any clause is,
+ *     the call ends with status ALLL_PROP_CONFLICT, conflict_clause = the smallest falsified clause
+ *     index, and the round applies nothing (the thresholds are those of the round's start);
+ *  3. otherwise a clause with no true literal whose free literals all are one literal is a unit and
+ *     forces it (x x !y with y pinned 1 is a unit; x !x is not);
+ *  4. no unit: ALLL_PROP_FIXPOINT;
+ *  5. max_rounds != 0 and that many rounds already applied: ALLL_PROP_ROUND_CAP, nothing applied;
+ *  6. otherwise every forced literal is applied at once: thr[v] = 0xFFFFFFFF for a forced 2v, 0 for a
+ *     forced 2v+1; a variable forced both ways in one round is pinned to 1 (the next round finds the
+ *     clause that wanted 0 falsified); rounds += 1, n_forced += the variables changed.
+ * The result does not depend on any execution order. */
+#define ALLL_PROP_FIXPOINT 0
+#define ALLL_PROP_CONFLICT 1
+#define ALLL_PROP_ROUND_CAP 2
+#define ALLL_PROP_NONE 3          /* group / batch item without thresholds: left alone */
+typedef struct alll_propagate_result {
+    uint64_t conflict_clause;     /* n_clauses when there is none (item-local index in a group / batch) */
+    uint64_t n_forced;            /* variables this call pinned */
+    uint32_t rounds;              /* rounds that applied something */
+    int32_t status;               /* ALLL_PROP_* */
+} alll_propagate_result;          /* 24 bytes */
+/* Propagates the pins of the context's thresholds on the device (max_rounds = 0: until a fixpoint or
+ * a conflict, at most n_vars + 1 rounds).  Allowed only while n_iterations == 0, on a context that
+ * has thresholds, else ALLL_ERR_INVALID_ARG (the message says which); it refuses the contexts
+ * alll_set_var_thresholds refuses, with ALLL_ERR_UNSUPPORTED.  Afterwards the context is, bit for
+ * bit, a fresh context given the propagated thresholds through alll_set_var_thresholds (the
+ * assignment is rewritten with the biased fill); a second call returns the same status with
+ * rounds == 0 and n_forced == 0 (after ALLL_PROP_ROUND_CAP it makes up to max_rounds more rounds).  It may come before or after alll_track_best.  A conflict leaves
+ * the context usable (the loop then runs to max_iters, as above).
+ * alll_get_var_thresholds copies the context's thresholds (n == n_vars), the propagated ones after
+ * the call above; a context without thresholds: ALLL_ERR_INVALID_ARG.  (No reference counterpart.) */
+int alll_propagate_pins(alll_ctx* ctx, uint64_t max_rounds, alll_propagate_result* res);
+int alll_get_var_thresholds(alll_ctx* ctx, uint32_t* out, uint64_t n);
 
 /* Introspection of the last iteration (parity tests): violated bitmask of the last eval
  * pass (ceil(n_clauses/64) words) and the MIS picked from it (ascending clause order). */
@@ -362,6 +405,14 @@ int alll_batch_set_slice(alll_batch* b, uint64_t iters_per_launch);
  * ALLL_BATCH_FIRST_SOLVED, items that are one instance under different pinned variables make a cube
  * portfolio (alll_pinned_conflict drops the cubes that cannot be met). */
 int alll_batch_set_var_thresholds(alll_batch* b, uint64_t item, const uint32_t* thr, uint64_t n);
+/* alll_propagate_pins for every item that has thresholds (results: n_items entries), in one kernel
+ * launch, a workgroup per item: item i's result, thresholds and refilled words are exactly those of
+ * a context of its own; conflict_clause is the item's own clause index.  An item without thresholds
+ * is left alone and gets ALLL_PROP_NONE.  Refused with ALLL_ERR_INVALID_ARG when any item has made
+ * an iteration.  alll_batch_get_var_thresholds copies one item's thresholds (n == its n_vars; an
+ * item without thresholds: ALLL_ERR_INVALID_ARG). */
+int alll_batch_propagate_pins(alll_batch* b, uint64_t max_rounds, alll_propagate_result* results);
+int alll_batch_get_var_thresholds(alll_batch* b, uint64_t item, uint32_t* out, uint64_t n);
 /* alll_track_best / alll_get_best per item (the contract above): switched for every
  * item at once, while no item has made an iteration (else ALLL_ERR_INVALID_ARG); every item keeps
  * its own record, in its own pass count, exactly that of a tracking context created from it.  The
@@ -422,6 +473,15 @@ int alll_group_set_assignment_words(alll_group* g, uint64_t item, const uint32_t
  * ALLL_GROUP_FIRST_SOLVED, items that are one instance under different pinned variables make a
  * cube portfolio: the first cube solved wins. */
 int alll_group_set_var_thresholds(alll_group* g, uint64_t item, const uint32_t* thr, uint64_t n);
+/* alll_propagate_pins over the union, all items at once (results: n_items entries): a global round
+ * is every unfinished item's own round, and item i's result, thresholds and refilled words are
+ * exactly those of a context of its own (rounds, forced count, the conflict clause in its local
+ * index).  An item that has ended takes no further part and disturbs no other item; an item without
+ * thresholds is left alone and gets ALLL_PROP_NONE.  Only before the group's first iteration.
+ * alll_group_get_var_thresholds copies one item's thresholds (n == its n_vars; an item without
+ * thresholds: ALLL_ERR_INVALID_ARG). */
+int alll_group_propagate_pins(alll_group* g, uint64_t max_rounds, alll_propagate_result* results);
+int alll_group_get_var_thresholds(alll_group* g, uint64_t item, uint32_t* out, uint64_t n);
 /* alll_track_best / alll_get_best per item (the contract above): switched for every
  * item at once, before the group's first iteration; the same ALLL_ERR_UNSUPPORTED contexts.  Every
  * item keeps its own record, in its local variable numbering and its own pass count, exactly that
@@ -498,6 +558,13 @@ int alll_biased_initial_assignment(uint64_t seed, uint32_t n_vars, const uint32_
  * ALLL_ERR_INVALID_ARG; offsets that do not start at 0 or decrease: ALLL_ERR_BAD_INPUT; a literal
  * of a variable >= n_vars: ALLL_ERR_LITERAL_RANGE (*clause is then left alone). */
 int alll_pinned_conflict(const alll_problem* prob, const uint32_t* thr, uint64_t n, uint64_t* clause);
+
+/* The propagation of alll_propagate_pins on the host (the semantics above): thr (n == n_vars
+ * entries) is updated in place.  Validation and error codes are those of alll_pinned_conflict;
+ * nothing is written on an error.  Status ALLL_PROP_CONFLICT with rounds == 0 holds exactly when
+ * alll_pinned_conflict reports the same clause. */
+int alll_pinned_propagate(const alll_problem* prob, uint32_t* thr, uint64_t n, uint64_t max_rounds,
+                          alll_propagate_result* res);
 
 /* The reference's own initial assignment (VariablesArray.h:23-34) in the reference-RNG mode
  * (ALLL_FLAG_REFERENCE_RNG): `rd_state` is the random_device stand-in's state
