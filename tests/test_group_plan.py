@@ -150,6 +150,30 @@ def test_swarm_plan_matches_the_numpy_restatement(plan, native, fixed):
     assert r["literals"] == [int(x) for x in lits]
 
 
+def test_ladder_plan_matches_the_numpy_restatement(plan):
+    """The ladder of tests/prop_cases.py (the propagation's group case): items of 1 to 5 words, clauses
+    of width 2, 1 and 0, and the clause bases that a clauseless item shares with the item behind it,
+    which the propagation's scan searches."""
+    import prop_cases as P
+
+    c = P.ladder()
+    items, seeds = c["items"], c["seeds"]
+    r = plan(items, [(i, s) for i, s in enumerate(seeds)])
+    assert r["rc"] == OK
+    n_vars, offs, lits, places = compose(items)
+    assert r["shape"] == [n_vars, offs.size - 1, 334]
+    bases = [pl["clause_base"] for pl in places] + [offs.size - 1]
+    assert r["clause_base"] == bases
+    for j in range(len(items)):
+        assert (bases[j] == bases[j + 1]) == (P.ladder_kind(j) == "clauseless" or j == 0), j
+    for it, pl, s in zip(r["item"], places, seeds):
+        assert it == [s, pl["lit_base"], pl["n_vars"], pl["n_words"], pl["var_base"], pl["word_base"], pl["clause_base"],
+                      pl["n_clauses"]]
+    w = r["words"]
+    assert [tuple(w[4 * i:4 * i + 4]) for i in range(len(w) // 4)] == word_table(items, seeds)
+    assert r["offsets"] == [int(x) for x in offs] and r["literals"] == [int(x) for x in lits]
+
+
 def test_item_errors_name_the_item(plan):
     good = ksat(50, 20, 3, 4)
     n, offs, lits = good

@@ -48,6 +48,41 @@ def test_round_cap_continues_where_it_stopped(native):
     np.testing.assert_array_equal(thr, full["out"])
 
 
+def many_cases():
+    """The many-item cases of tests/test_gpu_prop_swarm.py: (name, case under max_rounds) -> the items with thresholds."""
+    return {"ladder": lambda cap: P.ladder(P.N_LADDER, cap), "prop_swarm": P.prop_swarm,
+            "limit": lambda cap: P.many([P.limit_instance()] * len(P.LIMIT_CUBES), [0] * len(P.LIMIT_CUBES),
+                                        [P.limit_item(cs)["thr"] for cs in range(len(P.LIMIT_CUBES))], cap)}
+
+
+@pytest.mark.parametrize("max_rounds", [0, 1, 10])
+@pytest.mark.parametrize("name", ["ladder", "prop_swarm", "limit"])
+def test_many_items_match_the_reference(native, name, max_rounds):
+    """Every item with thresholds of the ladder, the prop swarm and the limit item under its four cubes,
+    uncapped and capped at 1 and 10 rounds; a capped item is continued to the uncapped reference."""
+    from alllsatisfiabilitysolver_amd import propagate_pins
+
+    make = many_cases()[name]
+    c, full = make(max_rounds), make(0)
+    rest = P.continued(full, c)
+    checked = capped = 0
+    for i, ((n, offs, lits), thr) in enumerate(zip(c["items"], c["thrs"])):
+        if thr is None:
+            continue
+        out, res = propagate_pins(n, offs, lits, thr, max_rounds)
+        assert res == c["ress"][i], (name, i)
+        np.testing.assert_array_equal(out, c["outs"][i], err_msg=f"{name} item {i}")
+        if res["status"] == P.ROUND_CAP:
+            out, res = propagate_pins(n, offs, lits, out, 0)
+            assert res == rest[i], (name, i)
+            np.testing.assert_array_equal(out, full["outs"][i], err_msg=f"{name} item {i}, continued")
+            capped += 1
+        checked += 1
+    assert checked == {"ladder": 109, "prop_swarm": 669, "limit": 4}[name]
+    # (no item of the prop swarm or of the limit cubes makes more than five rounds)
+    assert (capped > 0) == (max_rounds == 1 or (name, max_rounds) == ("ladder", 10))
+
+
 def call(native, n, offs, lits, thr, max_rounds=0):
     prob = native.Problem(n, 0, offs.size - 1, offs.ctypes.data_as(u64p), lits.ctypes.data_as(u32p))
     res = native.PropagateResult(12345, 12345, 12345, 12345)
@@ -143,6 +178,32 @@ def test_sanitized_matches_the_reference(dump, name):
     again = ["100", "100"] if name == "C_cap" else ["0", "0"]  # (the capped chain goes on: 100 more rounds)
     assert rows[2] == ["rc", "0"] and rows[3] == ["res", want[0], *again, want[3]]
     np.testing.assert_array_equal(np.frombuffer(o.read_bytes(), "<u4"), c["out"])
+
+
+@pytest.mark.parametrize("max_rounds", [0, 10])
+def test_sanitized_ladder_union(dump, max_rounds):
+    """The ladder's plain and clauseless items as one instance (group_cases.compose; the padding
+    variables between the items are fair coins): 129 rounds in which every round ends another chain,
+    and the cap at 10 with its continuation."""
+    from group_cases import compose
+
+    d, run = dump
+    lad = P.ladder()
+    keep = [j for j in range(P.N_LADDER) if P.ladder_kind(j) in ("plain", "clauseless")]
+    n, offs, lits, places = compose([lad["items"][j] for j in keep])
+    thr = np.full(n, P.FAIR, np.uint32)
+    for j, p in zip(keep, places):
+        thr[p["var_base"]:p["var_base"] + p["n_vars"]] = lad["thrs"][j]
+    out, res = P.propagate(n, offs, lits, thr, max_rounds)
+    forced = sum(min(lad["ress"][j]["rounds"], max_rounds or 129) for j in keep)
+    assert res == dict(status=P.ROUND_CAP if max_rounds else P.FIXPOINT, rounds=max_rounds or 129, n_forced=forced,
+                       conflict_clause=offs.size - 1)
+    f, o = d / f"ladder{max_rounds}.bin", d / f"ladder_out{max_rounds}.bin"
+    f.write_bytes(pack(n, offs, lits, thr))
+    rows = run(f, max_rounds, o)
+    assert rows[:2] == [["rc", "0"], ["res", str(res["status"]), str(res["rounds"]), str(forced), str(offs.size - 1)]]
+    assert rows[2] == ["rc", "0"] and rows[3][:3] == (["res", str(P.ROUND_CAP), "10"] if max_rounds else ["res", "0", "0"])
+    np.testing.assert_array_equal(np.frombuffer(o.read_bytes(), "<u4"), out)
 
 
 @pytest.mark.parametrize("case", [c for c in CONFLICT_CASES if c[5] != OK], ids=lambda c: c[0])
