@@ -59,13 +59,13 @@ EXPORTED = [
     "alll_get_stats", "alll_verify", "alll_get_assignment", "alll_set_assignment",
     "alll_get_assignment_words", "alll_set_assignment_words", "alll_get_violated_mask",
     "alll_get_mis", "alll_bench_eval", "alll_profile", "alll_loop_times", "alll_synchronize", "alll_eval_bytes",
-    "alll_layout", "alll_eval_kernel", "alll_comm_size", "alll_uses_graphs", "alll_rr_pass_log", "alll_rr_barrier_timeouts", "alll_initial_assignment", "alll_reference_initial_assignment", "alll_shard_plan", "alll_plan_multi_gpu", "alll_dimacs_parse", "alll_dimacs_read", "alll_generate_ksat",
+    "alll_layout", "alll_eval_kernel", "alll_comm_size", "alll_uses_graphs", "alll_rr_pass_log", "alll_rr_barrier_timeouts", "alll_epoch_counters", "alll_initial_assignment", "alll_reference_initial_assignment", "alll_shard_plan", "alll_plan_multi_gpu", "alll_dimacs_parse", "alll_dimacs_read", "alll_generate_ksat",
     "alll_batch_fits", "alll_batch_create", "alll_batch_destroy", "alll_batch_solve", "alll_batch_run",
     "alll_batch_get_stats", "alll_batch_get_assignment_words", "alll_batch_set_assignment_words",
     "alll_batch_set_slice",
     "alll_group_create", "alll_group_destroy", "alll_group_solve", "alll_group_run", "alll_group_get_stats",
     "alll_group_get_assignment_words", "alll_group_set_assignment_words", "alll_group_layout",
-    "alll_group_eval_kernel",
+    "alll_group_eval_kernel", "alll_group_epoch_counters",
     "alll_var_threshold", "alll_biased_initial_assignment", "alll_set_var_thresholds",
     "alll_group_set_var_thresholds", "alll_batch_set_var_thresholds", "alll_pinned_conflict",
     "alll_track_best", "alll_get_best", "alll_group_track_best", "alll_group_get_best",
@@ -194,6 +194,7 @@ _SIGS = {
     "alll_uses_graphs": ([_vp, ctypes.POINTER(ctypes.c_char_p)], ctypes.c_int),
     "alll_rr_pass_log": ([_vp, _u32p, ctypes.c_uint32], ctypes.c_int),
     "alll_rr_barrier_timeouts": ([_vp], ctypes.c_int64),
+    "alll_epoch_counters": ([_vp, _u64p], ctypes.c_int),
     "alll_shard_plan": ([ctypes.c_uint64, ctypes.c_int, ctypes.c_int, _u64p, _u64p, _u64p], ctypes.c_int),
     "alll_reference_initial_assignment": ([ctypes.c_uint64, ctypes.c_uint32, _u8p], ctypes.c_int),
     "alll_plan_multi_gpu": ([ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p],
@@ -223,6 +224,7 @@ _SIGS = {
     "alll_group_set_assignment_words": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
     "alll_group_layout": ([_vp], ctypes.c_int),
     "alll_group_eval_kernel": ([_vp], ctypes.c_char_p),
+    "alll_group_epoch_counters": ([_vp, _u64p], ctypes.c_int),
     "alll_var_threshold": ([ctypes.c_double, _u32p], ctypes.c_int),
     "alll_biased_initial_assignment": ([ctypes.c_uint64, ctypes.c_uint32, _u32p, _u8p], ctypes.c_int),
     "alll_set_var_thresholds": ([_vp, _u32p, ctypes.c_uint64], ctypes.c_int),

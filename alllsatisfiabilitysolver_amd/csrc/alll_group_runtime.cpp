@@ -415,4 +415,9 @@ int alll_group_layout(alll_group* g) { return g ? alll_layout(g->ctx) : -1; }
 
 const char* alll_group_eval_kernel(alll_group* g) { return g ? alll_eval_kernel(g->ctx) : ""; }
 
+int alll_group_epoch_counters(alll_group* g, uint64_t out[4]) {
+    if (!g || !out) return fail(ALLL_ERR_INVALID_ARG, "null argument");
+    return alll_epoch_counters(g->ctx, out);
+}
+
 }  // extern "C"

@@ -36,6 +36,14 @@ constexpr uint32_t RANGED_MAX_TILES = 16;          // tiles per block pass (64-b
 // Every LFMIS round decides at least the lowest undecided clause, so rounds <= |U|; the cap
 // only bounds a kernel that would otherwise run away on a bug or an adversarial chain.
 constexpr uint32_t MAX_TAIL_ROUNDS = 1u << 20;
+// Owner epochs of the one-set loop (32-bit): an iteration that starts at epoch R
+// uses the epochs R .. R + grid rounds + tail rounds, at most GRID_ROUNDS_MAX + MAX_TAIL_ROUNDS
+// more (alll_create caps alll_options.grid_rounds; the split changes no result).  The tail starts
+// the epochs over (owner cleared, round_next = 1) when the epoch it hands to the next iteration has
+// reached EP_RESTART_AT, so no iteration can reach 2^32.  A constant: the tail tests it on
+// registers alone.
+constexpr uint32_t GRID_ROUNDS_MAX = 64;
+constexpr uint32_t EP_RESTART_AT = 0u - (GRID_ROUNDS_MAX + MAX_TAIL_ROUNDS + 2u);
 // Bucketed LFMIS round 0 (fixed width K): every claim of round 0 becomes a 64-bit pair
 // {clause id:32 | lose:1 | entry index in its run:16 | variable offset in its bucket:15},
 // written grouped by variable bucket (bkt_width variables) inside its run (run_tiles
@@ -60,7 +68,13 @@ constexpr uint32_t FP_B = 2048;            // entries per block of the count / t
 constexpr uint32_t FP_G = 4;       // grid LFMIS rounds before the one-workgroup tail (2, 3, 5: slower)
 constexpr uint32_t FP_G_HOT = 6;   // ... on instances with hot variables (5, 7, 8, 10: slower)
 constexpr uint32_t FP_G_MAX = FP_G_HOT > FP_G ? FP_G_HOT : FP_G;
-constexpr uint32_t FP_MAX_DEFAULT = 64;    // LFMIS passes per iteration before k_rr_mw decides it
+// Least epoch budget B a cap may set (ALLL_RR_EP_BUDGET).  k_fp_sched lets a pass start at epoch e
+// only while e + FP_G_MAX + 1 < B: its grid rounds and one round of the tail.  An iteration's
+// first pass is not tested; it starts at e <= B / 2 - 1 (at B / 2 the epochs restart), and
+// B / 2 - 1 + FP_G_MAX + 1 < B holds from B = 2 FP_G_MAX + 2 on.  Two more leave that pass's tail
+// a second round, so that an iteration is not bound to fail before it has decided anything.
+constexpr uint32_t FP_EP_CAP_MIN = 2 * (FP_G_MAX + 2);
+constexpr uint32_t FP_MAX_DEFAULT = 64;   // LFMIS passes per iteration before k_rr_mw decides it
 // incremental passes: defaults of LoopBuffers::fp_rep_cap / fp_rw_min / fp_rw_timeout
 constexpr uint32_t FP_REP_CAP = 1u << 16;   // dirty entries per round before the pass gives up (a full pass follows)
 constexpr uint32_t FP_RW_GRID = 64;         // workgroups of the wide repair (one per CU, all resident)
@@ -116,7 +130,11 @@ struct RRFpCtl {
     uint32_t pbsrc;      // the last pass was incremental: its picks are the bits fp_pbits (k_fp_turn reads
                          // them there), not bit 0 of fp_in
     uint32_t rw_timeouts;  // wide-round grid barriers that timed out (never reset; alll_rr_barrier_timeouts)
-    uint32_t spare[3];
+    uint32_t ep_restarts;  // iterations that started the owner epochs over (restart bit 0; never reset;
+                           // alll_epoch_counters)
+    uint32_t ep_fails;     // iterations that went to FP_FAIL because their epochs ran out -- not those that ran
+                           // out of cover serials or passes (never reset; alll_epoch_counters)
+    uint32_t spare[1];
 };
 static_assert(sizeof(RRFpCtl) == 128, "RRFpCtl: 32 words");
 // Streaming solve with T > 1 threads (SATInstance::solve(getEnumeratedClause, n, batch),
@@ -182,7 +200,8 @@ struct DevState {
     uint32_t rd_draws;     // reference-RNG mode: the round's draws
     uint32_t rd_n;         // reference-RNG mode: engine positions the parallel draws consider
     uint32_t rd_fail;      // reference-RNG mode: the parallel draws ran past rd_n (sequential redo)
-    uint32_t rd_pad;
+    uint32_t ep_restarts;  // times the one-set loop started its owner epochs over (k_tail; create, when
+                           // ALLL_EPOCH0 lies past the restart point; alll_epoch_counters)
     // best-assignment tracking (maintained by the reduce while LoopBuffers::A_best is set)
     uint64_t best_u;       // fewest violated clauses an eval pass of the loop found (~0: no pass yet)
     uint64_t best_iter;    // n_iter of the first pass that found them (0: no pass yet)
@@ -243,7 +262,9 @@ struct LoopBuffers {
     uint32_t* mis;          // per tile: TILE slots of MIS clause ids
     uint32_t* left;         // compact list of undecided entries handed to the tail kernel
     uint32_t* tmis;         // MIS clauses decided by the tail kernel
-    unsigned long long* owner; // n_vars 64-bit owner keys (epoch-tagged, never reset)
+    unsigned long long* owner; // 64-bit owner keys (epoch-tagged), n_vars or, with hot variables, one per
+                               // vmix slot; cleared only when the epochs start over, once in ~2^32
+                               // rounds (k_tail)
     uint8_t* cover;         // per variable: stamp of the iteration whose MIS covers it (the
                             // reduce clears it when the stamp cycles back to 1)
     unsigned long long* tile_stats; // per tile: [2t] sum |MIS|, [2t+1] sum resampled literals
@@ -352,6 +373,7 @@ struct LoopBuffers {
     unsigned long long fp_rw_timeout;  // wide-round grid barrier timeout, 100 MHz ticks (FP_RW_TIMEOUT; tests)
     uint32_t fp_inc_after;      // full passes of an iteration before the incremental ones
     uint32_t fp_ib, fp_tb;      // key bits of the entry index and of the turn
+    uint32_t fp_ep_cap;         // cap on the epoch budget of the key layout, 0 = none (ALLL_RR_EP_BUDGET; tests)
     uint32_t fp_hot;            // the instance has hot variables (more grid rounds per pass)
     uint32_t fp_max;            // LFMIS passes per iteration
     // streaming solve with T > 1 threads (srr_T > 0; nullptr otherwise)

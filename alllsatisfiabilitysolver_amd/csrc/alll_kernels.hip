@@ -1139,6 +1139,7 @@ __device__ void fp_begin_body(const LoopBuffers& b) {
     if (threadIdx.x == 0) {
         const bool ep0 = fp_ep_restart(b, ctl), ser0 = fp_serial_restart(b, ctl);
         ctl->restart = (ep0 ? 1u : 0u) | (ser0 ? 2u : 0u);
+        if (ep0) ctl->ep_restarts += 1;
         ctl->state = FP_RUN;
         ctl->nu = nu;
         ctl->fp_iter = 0;
@@ -2066,6 +2067,29 @@ __global__ __launch_bounds__(BJN_THREADS) void k_bjoin(ClauseView cv, LoopBuffer
     }
 }
 
+// The owner epochs are 32 bits of the key, and a key of a later epoch must be smaller than every
+// stale one, so the epochs must never reach 2^32.  The tail, the last kernel of an iteration to
+// touch the owner keys, hands `next` to the following iteration (whose pre-reduce scatter is the
+// first to use it); once next >= EP_RESTART_AT (alll_internal.h) its workgroup clears the keys and
+// the epochs start over at 1, as after create.  An iteration that starts below EP_RESTART_AT ends
+// below 2^32: it uses at most GRID_ROUNDS_MAX + MAX_TAIL_ROUNDS epochs more.  The clear is one
+// workgroup's stores over the keys once in ~2^32 rounds, and nothing is decided on the host
+// or at capture: a graph replays the same test.  Ranks of a sharded run decide every iteration's
+// LFMIS alike, so `next` -- a function of the trajectory alone -- makes them restart in the same
+// iteration.  Every thread of the workgroup calls it with the same `next`, after its last access
+// to the keys (a barrier between); true: the epochs started over (thread 0 wrote round_next).
+__device__ __forceinline__ bool epochs_start_over(const LoopBuffers& b, uint32_t next) {
+    if (next < EP_RESTART_AT) return false;
+    // (a key per variable, or per vmix slot of an instance with hot variables)
+    const uint64_t n_keys = b.vmix_mask == 0xFFFFFFFFu ? (uint64_t)b.n_vars : (uint64_t)b.vmix_mask + 1u;
+    for (uint64_t i = threadIdx.x; i < n_keys; i += blockDim.x) b.owner[i] = ~0ull;
+    if (threadIdx.x == 0) {
+        b.state->round_next = 1;
+        b.state->ep_restarts += 1;
+    }
+    return true;
+}
+
 // Tail: one workgroup finishes the LFMIS over the compact list handed over by the last grid
 // round (CLAIM / barrier / JOIN passes until no undecided clause is left).  Entries are
 // processed in chunks of one per thread; survivors are compacted in place (a write position
@@ -2084,7 +2108,13 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tail(ClauseView cv, LoopBuffer
     if (b.n_tiles) load_ent<K>(e0, b.left + (uint64_t)threadIdx.x * S);
     const uint32_t active = st->active, stamp = st->stamp, n0 = st->left_cnt, rbase = st->round_base;
     spec_fence();
-    if (!active) return;
+    if (!active) {
+        // (a capped or solved pass: its reduce took one epoch, and the loop may go on after it)
+        const uint32_t next = st->round_next;
+        __syncthreads();  // (every thread has read it before thread 0 may write it)
+        (void)epochs_start_over(b, next);
+        return;
+    }
     __shared__ uint32_t s_wp, s_tm;
     uint32_t n = n0;
     uint32_t epoch = rbase + first_round;
@@ -2164,8 +2194,12 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tail(ClauseView cv, LoopBuffer
         __syncthreads();
     }
     __syncthreads();
+    // the first unused epoch: past the reduce's (rbase + 1) and every epoch of the rounds; no thread
+    // touches the owner keys after the barrier above, so they may be cleared here
+    const uint32_t next = max(rbase + 1u, epoch);
+    const bool over = epochs_start_over(b, next);
     if (threadIdx.x == 0) {
-        if (epoch > st->round_next) st->round_next = epoch;
+        if (!over) st->round_next = next;
         st->tail_rounds = rounds;
         st->tmis_cnt = s_tm;
         const uint32_t total = first_round + rounds;
@@ -3304,7 +3338,8 @@ __device__ __forceinline__ unsigned long long fp_key(const LoopBuffers& b, uint3
 // epochs one iteration may use (keys of later epochs are smaller)
 __device__ __forceinline__ uint32_t fp_ep_budget(const LoopBuffers& b) {
     const uint32_t eb = 64 - b.fp_tb - b.fp_ib;
-    return eb >= 31 ? 0x7FFFFFFFu : (1u << eb) - 1u;
+    const uint32_t nat = eb >= 31 ? 0x7FFFFFFFu : (1u << eb) - 1u;
+    return b.fp_ep_cap ? min(nat, b.fp_ep_cap) : nat;  // (the cap: tests; the key layout keeps its epoch bits)
 }
 
 // the variables of scan entry i: the entry's first 4 (KW = 4: every clause is that narrow),
@@ -4068,7 +4103,7 @@ __global__ __launch_bounds__(1024) void k_fp_tail(ClauseView cv, LoopBuffers b, 
     if (threadIdx.x == 0) {
         ctl->ep_next = ep;
         ctl->ran = 1;
-        if (failed) ctl->state = FP_FAIL;
+        if (failed) { ctl->state = FP_FAIL; ctl->ep_fails += 1; }
     }
 }
 
@@ -5021,7 +5056,9 @@ __device__ __forceinline__ void fp_sched_core(const LoopBuffers& b, RRFpCtl* ctl
             if (test) ctl->fp_iter += 1;
             ctl->ep_base = ctl->ep_next;
             ctl->serial = ctl->serial + 1u;  // 8-bit cover serials: at most 255 passes per iteration
-            if (ctl->ep_base + FP_G_MAX + 1u >= fp_ep_budget(b) || ctl->serial > 255u) ctl->state = FP_FAIL;
+            const bool ep_out = ctl->ep_base + FP_G_MAX + 1u >= fp_ep_budget(b);
+            if (ep_out) ctl->ep_fails += 1;
+            if (ep_out || ctl->serial > 255u) ctl->state = FP_FAIL;
         }
     }
 }

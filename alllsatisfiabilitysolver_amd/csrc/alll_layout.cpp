@@ -413,6 +413,14 @@ Knobs read_knobs() {
     if (const char* e = getenv("ALLL_RR_RW_MIN")) k.rr_rw_min = (uint32_t)std::max(0, atoi(e));
     if (const char* e = getenv("ALLL_RR_RW_TIMEOUT")) k.rr_rw_timeout = strtoull(e, nullptr, 10);
     if (const char* e = getenv("ALLL_RR_INC_AFTER")) k.rr_inc_after = (uint32_t)std::max(1, atoi(e));
+    // tests: a small epoch budget, so that small instances restart their owner epochs and run out of
+    // them (FP_EP_CAP_MIN: the least budget with which an iteration still makes a pass)
+    if (const char* e = getenv("ALLL_RR_EP_BUDGET"))
+        k.rr_ep_budget = (uint32_t)std::max<unsigned long long>(FP_EP_CAP_MIN, std::min<unsigned long long>(0x7FFFFFFFull, strtoull(e, nullptr, 10)));
+    // tests: the one-set loop's first owner epoch, so that a short run reaches the end of the 32-bit epochs
+    // (at least 1, the epoch create starts at and a restart goes back to)
+    if (const char* e = getenv("ALLL_EPOCH0"))
+        k.epoch0 = (uint32_t)std::max<unsigned long long>(1, std::min<unsigned long long>(0xFFFFFFFFull, strtoull(e, nullptr, 10)));
     // (test knob: fewer engine positions, so that the parallel draws run past them and the
     // one-thread chain redoes the round)
     if (const char* e = getenv("ALLL_RRNG_NMAX"))
@@ -465,6 +473,7 @@ int plan_instance(const alll_problem& prob, const alll_options& opt, const Knobs
     l.own_c1 = std::min<uint64_t>(m, (uint64_t)l.b.own_end * TILE);
     l.b.n_words = (l.n_vars + 31) / 32;
     l.b.win_words = kn.win_words;
+    l.epoch0 = kn.epoch0;
     // Ragged widths, T = 1, not streaming: chunk-transposed copy for k_eval_ragged (the CSR
     // arrays stay: the LFMIS kernels read clauses by id).  ALLL_FLAG_GENERIC_CSR and
     // ALLL_FLAG_NO_RANGED keep the clause-order CSR evaluation.  (the padding literal
@@ -485,6 +494,7 @@ int plan_instance(const alll_problem& prob, const alll_options& opt, const Knobs
     l.b.fp_tb = tb;
     l.b.fp_hot = l.cv.n_hot ? 1 : 0;
     l.b.fp_max = kn.rr_fp_max;  // passes per iteration (graph unroll)
+    l.b.fp_ep_cap = kn.rr_ep_budget;
     // incremental passes on instances without hot variables
     if (l.cv.n_hot || !kn.rr_inc) return ALLL_OK;
     l.b.fp_inc = 1;

@@ -25,6 +25,8 @@ struct Knobs {
     uint32_t rr_rw_min = FP_RW_MIN;     // ALLL_RR_RW_MIN: >= 0
     unsigned long long rr_rw_timeout = FP_RW_TIMEOUT;  // ALLL_RR_RW_TIMEOUT
     uint32_t rr_inc_after = 1;          // ALLL_RR_INC_AFTER: >= 1
+    uint32_t rr_ep_budget = 0;          // ALLL_RR_EP_BUDGET: >= FP_EP_CAP_MIN, 0 unset (no cap)
+    uint32_t epoch0 = 1;                // ALLL_EPOCH0: the first owner epoch of the one-set loop (32-bit)
     uint64_t rrng_nmax = ~0ull;         // ALLL_RRNG_NMAX: >= 8 (unset or empty: no cap)
     bool has_bucket_min_u = false;      // ALLL_BUCKET_MIN_U
     uint64_t bucket_min_u = 0;
@@ -60,6 +62,7 @@ struct Layout {
     std::vector<uint8_t> is_hot;          // per variable (empty: no hot variable)
     bool fp = false;                      // round robin by fixpoint
     uint32_t fp_slots = 8;                // variable slots per scan entry: 4 when every width <= 4
+    uint32_t epoch0 = 1;                  // DevState::round_next at create (before the restart rule, EP_RESTART_AT)
     // ---- plan_buckets
     uint64_t vrange = 0;                  // owner slots / bucketed variable keys
     std::vector<uint32_t> fp_soff, fp_breg;  // round robin: claimant list starts, bucket regions

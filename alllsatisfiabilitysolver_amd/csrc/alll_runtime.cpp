@@ -876,7 +876,8 @@ void set_shape(alll_ctx* c, const alll_options& opt, const Knobs& kn, const Layo
     if (!c->use_graph) c->graph_note = "ALLL_FLAG_NO_GRAPH";
     // skewed instances need more rounds before the leftovers are few enough for the
     // single-workgroup tail (power-law 3-SAT at 10M clauses: 10 rounds)
-    c->grid_rounds = opt.grid_rounds ? opt.grid_rounds : (l.cv.n_hot ? SKEWED_GRID_ROUNDS : DEFAULT_GRID_ROUNDS);
+    // (at most GRID_ROUNDS_MAX: the margin of the owner epochs' restart, EP_RESTART_AT, counts on it)
+    c->grid_rounds = opt.grid_rounds ? std::min(opt.grid_rounds, GRID_ROUNDS_MAX) : (l.cv.n_hot ? SKEWED_GRID_ROUNDS : DEFAULT_GRID_ROUNDS);
     c->small_u = kn.small_u;
     c->fuse_scatter = kn.fuse_scatter;
     c->tiles_per_rank = l.tiles_per_rank;
@@ -1140,7 +1141,11 @@ int alll_create(const alll_problem* prob, const alll_options* opt_in, alll_ctx**
     memset(c->h_state, 0, sizeof(DevState));
     c->h_state->limit_eval = ~0ull;
     c->h_state->limit_nores = ~0ull;
-    c->h_state->round_next = 1;
+    c->h_state->round_next = std::max<uint32_t>(1, lay.epoch0);
+    if (c->h_state->round_next >= EP_RESTART_AT) {  // (ALLL_EPOCH0 past the restart point: the tail's rule, on fresh keys)
+        c->h_state->round_next = 1;
+        c->h_state->ep_restarts = 1;
+    }
     c->h_state->best_u = ~0ull;
     if (lay.refrng) c->h_state->rd_state = opt.seed;  // (the random_device stand-in's state)
     if (hipMemcpyAsync(b.state, c->h_state, sizeof(DevState), hipMemcpyHostToDevice, c->stream) != hipSuccess)
@@ -1679,6 +1684,24 @@ int64_t alll_rr_barrier_timeouts(alll_ctx* c) {
     RRFpCtl ctl;
     if (hipMemcpy(&ctl, c->b.fp_ctl, sizeof ctl, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return ctl.rw_timeouts;
+}
+
+int alll_epoch_counters(alll_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return fail(ALLL_ERR_INVALID_ARG, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    DevState st;
+    HIP_TRY(hipMemcpy(&st, c->b.state, sizeof st, hipMemcpyDeviceToHost));
+    out[0] = out[1] = 0;
+    if (c->b.fp_ctl) {
+        RRFpCtl ctl;
+        HIP_TRY(hipMemcpy(&ctl, c->b.fp_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+        out[0] = ctl.ep_restarts;
+        out[1] = ctl.ep_fails;
+    }
+    out[2] = st.ep_restarts;
+    out[3] = st.round_next;
+    return ALLL_OK;
 }
 
 int alll_comm_size(alll_ctx* c) {

@@ -397,6 +397,14 @@ class Solver:
             raise N.AlllError(N.ALLL_ERR_HIP, "alll_rr_barrier_timeouts failed")
         return n
 
+    def epoch_counters(self) -> dict:
+        """Owner-epoch counters since create (test support): round-robin iterations that started
+        their epochs over and those left to the batch kernel for want of epochs, restarts of the
+        one-set loop's 32-bit epochs, and that loop's first unused epoch."""
+        out = np.zeros(4, np.uint64)
+        N.check(self._L.alll_epoch_counters(self._ctx, _p(out, _u64p)), "epoch_counters")
+        return dict(zip(("rr_restarts", "rr_fails", "restarts", "round_next"), (int(x) for x in out)))
+
     def comm_size(self) -> int:
         """Ranks in the solve: the RCCL communicator's count (or world with a host exchange)."""
         n = int(self._L.alll_comm_size(self._ctx))
@@ -591,6 +599,12 @@ class GroupSolver(_ItemSolver):
 
     def eval_kernel(self) -> str:
         return self._L.alll_group_eval_kernel(self._h).decode()
+
+    def epoch_counters(self) -> dict:
+        """Solver.epoch_counters of the union."""
+        out = np.zeros(4, np.uint64)
+        N.check(self._L.alll_group_epoch_counters(self._h, _p(out, _u64p)), "group_epoch_counters")
+        return dict(zip(("rr_restarts", "rr_fails", "restarts", "round_next"), (int(x) for x in out)))
 
 
 def solve_portfolio(n_vars: int, offsets, literals, seeds, max_iters: int = 0):

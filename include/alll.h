@@ -92,7 +92,7 @@ typedef struct alll_options {
                                the clause-sharded exchange path on one GPU (a rehearsal of the
                                multi-GPU path; the results are the same) */
     uint32_t flags;         /* ALLL_FLAG_* */
-    uint32_t grid_rounds;   /* full-grid LFMIS rounds before the tail kernel (0 = default) */
+    uint32_t grid_rounds;   /* full-grid LFMIS rounds before the tail kernel (0 = default; at most 64) */
     uint64_t stream_batch;  /* 0: SATInstance::solve(vector<ClauseArray*>*) semantics.  > 0: the
                                streaming solve SATInstance::solve(getEnumeratedClause, n_clauses,
                                batch_size) (SATInstance.h:70-153) with this batch size and
@@ -344,6 +344,12 @@ int alll_rr_pass_log(alll_ctx* ctx, uint32_t* out, uint32_t n_words);
  * Non-zero means the repair's workgroups were not all resident (the GPU shared with other work).
  * (No reference counterpart: measurement) */
 int64_t alll_rr_barrier_timeouts(alll_ctx* ctx);
+/* Owner-epoch counters since alll_create: out[0] round-robin iterations that started their owner
+ * epochs over, out[1] round-robin iterations left to the batch kernel because their epochs ran out,
+ * out[2] times the one-set loop (n_threads == 1, groups) started its 32-bit owner epochs over,
+ * out[3] the one-set loop's first unused epoch.  (No reference counterpart: test support, the
+ * tests at the epochs' ends) */
+int alll_epoch_counters(alll_ctx* ctx, uint64_t out[4]);
 /* Ranks taking part in the clause-sharded solve: ncclCommCount of the RCCL communicator, or
  * alll_options.world with a host-staged exchange (1 on one GPU); -1 on failure.  (The
  * reference counterpart is the thread count of the -p path, example/main.cpp:76-84.) */
@@ -492,9 +498,10 @@ int alll_group_get_var_thresholds(alll_group* g, uint64_t item, uint32_t* out, u
 int alll_group_track_best(alll_group* g, int on);
 int alll_group_get_best(alll_group* g, uint64_t item, uint64_t* n_violated, uint64_t* iteration, uint32_t* words,
                         uint64_t n_words);
-/* alll_layout / alll_eval_kernel of the union. */
+/* alll_layout / alll_eval_kernel / alll_epoch_counters of the union. */
 int alll_group_layout(alll_group* g);
 const char* alll_group_eval_kernel(alll_group* g);
+int alll_group_epoch_counters(alll_group* g, uint64_t out[4]);
 
 /* ---- host-side helpers (no GPU needed) ---------------------------------------------- */
 

@@ -88,6 +88,7 @@ int main(int argc, char** argv) {
         num("skewed", l.skewed); num("bucketed", l.bucketed); num("run_tiles", l.b.run_tiles); num("n_runs", l.b.n_runs);
         num("bucket_min_u", l.bucket_min_u); num("windows", l.windows); num("lit_mask", l.cv.lit_mask);
         num("id_shift", l.cv.id_shift); num("id_bits", l.cv.id_bits); num("lits_nt", l.cv.lits_nt); num("t_chunk0", l.t_chunk0);
+        num("fp_ep_cap", l.b.fp_ep_cap); num("fp_ep_cap_min", FP_EP_CAP_MIN); num("fp_g_max", FP_G_MAX); num("epoch0", l.epoch0);
         vec("rr_sets", l.rr_sets); vec("is_hot", l.is_hot); vec("fp_soff", l.fp_soff); vec("fp_breg", l.fp_breg);
         vec("run_t0", l.run_t0); vec("flagged", l.flagged); vec("perm", l.perm); vec("lits_t", l.lits_t);
         vec("win_base", l.win_base); vec("rg_off", l.rg_off);

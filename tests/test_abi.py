@@ -101,6 +101,26 @@ def test_create_validates_input(native):
     assert ei.value.code == native.ALLL_ERR_BAD_INPUT
 
 
+@pytest.mark.parametrize("name", ["alll_epoch_counters", "alll_group_epoch_counters"])
+def test_epoch_counters_refuse_null_arguments(native, name):
+    """alll_epoch_counters(ctx, out[4]) and its group form: declared with four output words, exported,
+    and a null context or a null output is ALLL_ERR_INVALID_ARG with nothing written (the four words
+    a context writes are checked on the GPU, tests/test_gpu_epochs.py)."""
+    L = native.lib()
+    text = open(os.path.join(ROOT, "include", "alll.h")).read()
+    assert re.search(r"int %s\(\w+\* \w+, uint64_t out\[4\]\);" % name, text)
+    assert name in header_functions() and name in native.EXPORTED
+    f = getattr(L, name)
+    out = np.full(6, 0xABCD, np.uint64)
+    p = out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    assert f(None, p) == native.ALLL_ERR_INVALID_ARG
+    assert (out == 0xABCD).all()
+    assert f(None, None) == native.ALLL_ERR_INVALID_ARG
+    if name == "alll_epoch_counters":  # (a context that is never dereferenced: the output is tested first)
+        assert f(ctypes.c_void_p(out.ctypes.data), None) == native.ALLL_ERR_INVALID_ARG
+        assert (out == 0xABCD).all()
+
+
 def _ref_lists(ref):
     out, p = [], 0
     for n in ref["l_c_num"]:

@@ -303,6 +303,26 @@ def test_round_robin_claimant_buckets(dump, inst, mask, n_bkt):
     assert np.array_equal(r["fp_breg"], np.concatenate([[0], np.cumsum(per)]))
 
 
+def test_epoch_knobs_reach_the_plan(dump):
+    """ALLL_RR_EP_BUDGET caps the round robin's epoch budget (LoopBuffers::fp_ep_cap), clamped from
+    below to 2 (FP_G_MAX + 2) and from above to the key layout's 2^31 - 1; ALLL_EPOCH0 is the one-set
+    loop's first owner epoch (32-bit, at least 1).  Unset: no cap, and create's start at epoch 1."""
+    r = dump(C2, T=4)
+    assert (r["fp"], r["fp_ep_cap"], r["epoch0"]) == (1, 0, 1)
+    assert r["fp_ep_cap_min"] == 2 * (r["fp_g_max"] + 2) == 16
+    for given, want in ((4096, 4096), (17, 17), (16, 16), (15, 16), (1, 16), (0, 16), (2**31 - 1, 2**31 - 1),
+                        (2**31, 2**31 - 1), (2**40, 2**31 - 1)):
+        assert dump(C2, T=4, ALLL_RR_EP_BUDGET=given)["fp_ep_cap"] == want, given
+    # (the one-set loop and the batch kernel alone have no claim keys to budget: the cap stays 0)
+    assert dump(C2, ALLL_RR_EP_BUDGET=64)["fp_ep_cap"] == 0
+    assert dump(C2, T=4, ALLL_RR_FP=0, ALLL_RR_EP_BUDGET=64)["fp_ep_cap"] == 0
+    for given, want in ((1, 1), (0, 1), (2**31, 2**31), (2**32 - 3, 2**32 - 3), (2**32 - 1, 2**32 - 1), (2**32, 2**32 - 1),
+                        (2**40, 2**32 - 1)):
+        for T in (1, 4):
+            assert dump(C2, T=T, ALLL_EPOCH0=given)["epoch0"] == want, (given, T)
+    assert dump(C2, ALLL_EPOCH0=77, ALLL_RR_EP_BUDGET=99)["epoch0"] == 77
+
+
 @pytest.mark.parametrize("m", [1, 2, 3, 800, 2**20])
 def test_streaming_inverse(dump, m):
     r = dump(ksat(64, m, 1, 4), batch=64)
