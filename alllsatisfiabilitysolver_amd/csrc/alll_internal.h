@@ -52,6 +52,13 @@ constexpr uint32_t BKT_MAX = 4096;            // buckets (LDS histogram of k_bsc
 constexpr uint32_t BKT_SHIFT_MIN = 10;
 constexpr uint32_t BKT_SHIFT_MAX = 15;        // LDS minima of k_bresolve: 4 << 15 = 128 KiB
 constexpr uint32_t RUN_TILES_MAX = 16;        // entry index within a run < 16 * TILE = 2^16
+// Run record (LoopBuffers::run_rec): what the scatter of a run knows and k_bjoin needs, in one
+// line, so that the join loads it with the loop state instead of deriving it again.
+constexpr uint32_t RUN_REC_WORDS = 32;        // 128 bytes
+constexpr uint32_t RUN_REC_E = 0;             // entries of the run (violated clauses of its tiles)
+constexpr uint32_t RUN_REC_NP = 1;            // pairs of the run
+constexpr uint32_t RUN_REC_PRE = 2;           // prefix of the tile counts, RUN_TILES_MAX + 1 words
+static_assert(RUN_REC_PRE + RUN_TILES_MAX + 1 <= RUN_REC_WORDS, "the run record is one line");
 constexpr int BKT_THREADS = 512;
 constexpr uint32_t BKT_RUN_BATCH = 1024;        // runs per segment-table batch of k_bresolve
 constexpr unsigned long long PAIR_LOSE = 1ull << 31;
@@ -273,7 +280,8 @@ struct LoopBuffers {
     unsigned long long* ktime; // TIME_SLOTS x TIME_FIELDS stamps, nullptr = timing off
     unsigned long long* pairs;  // bucketed round 0: n_runs x run_tiles*TILE*K pairs (nullptr = atomics)
     unsigned long long* runtab; // [bucket][run]: start | count << 32 of the bucket's pairs in the run
-    uint32_t* run_pairs;        // pairs per run
+    uint32_t* run_rec;          // per run: RUN_REC_WORDS words (one 128-byte line) that the scatter hands
+                                // to k_bjoin: entries, pairs, prefix of the tile counts (RUN_REC_*)
     const uint32_t* win_base;   // hybrid eval: per tile, first assignment word of its LDS window
                                 // (nullptr: words [0, win_words) for every tile)
     uint32_t win_words;         // hybrid eval: LDS window size in words (<= LDS_WORDS)

@@ -305,12 +305,11 @@ struct ScatterLds {
     uint32_t* hist;               // BKT_MAX bucket counters / cursors
     uint32_t* hk;                 // HOT_SLOTS hot-table keys
     unsigned long long* hv;       // HOT_SLOTS hot-table minima
-    uint32_t* tc;                 // RUN_TILES_MAX tile counts
     uint32_t* pre;                // RUN_TILES_MAX + 1 prefix
     uint32_t* wsum;               // BSC_THREADS / 64
-    unsigned long long* pairs;    // BKT_STAGE staged pairs
+    unsigned long long* pairs;    // BKT_STAGE staged pairs (16-byte aligned)
 };
-constexpr size_t SCATTER_LDS_BYTES = 8 * BKT_STAGE + 8 * HOT_SLOTS + 4 * BKT_MAX + 4 * HOT_SLOTS + 4 * RUN_TILES_MAX +
+constexpr size_t SCATTER_LDS_BYTES = 8 * BKT_STAGE + 8 * HOT_SLOTS + 4 * BKT_MAX + 4 * HOT_SLOTS +
                                      4 * (RUN_TILES_MAX + 4) + 4 * (BSC_THREADS / 64);
 
 __device__ __forceinline__ ScatterLds carve_scatter_lds(void* base) {
@@ -320,15 +319,14 @@ __device__ __forceinline__ ScatterLds carve_scatter_lds(void* base) {
     L.hv = reinterpret_cast<unsigned long long*>(p); p += 8 * HOT_SLOTS;
     L.hist = reinterpret_cast<uint32_t*>(p); p += 4 * BKT_MAX;
     L.hk = reinterpret_cast<uint32_t*>(p); p += 4 * HOT_SLOTS;
-    L.tc = reinterpret_cast<uint32_t*>(p); p += 4 * RUN_TILES_MAX;
     L.pre = reinterpret_cast<uint32_t*>(p); p += 4 * (RUN_TILES_MAX + 4);
     L.wsum = reinterpret_cast<uint32_t*>(p);
     return L;
 }
 
 template <int K>
-__device__ void scatter_run(const ClauseView& cv, const LoopBuffers& b, uint32_t* list, uint32_t r, uint32_t epoch,
-                            const ScatterLds& L);
+__device__ void scatter_run(const ClauseView& cv, const LoopBuffers& b, uint32_t* list, uint32_t r, uint32_t t0,
+                            uint32_t nt, const uint32_t* lds_tc, uint32_t epoch, const ScatterLds& L);
 
 // ------------------------------------------------------------------------------------
 // Clause evaluation, fixed width K, chunk-transposed literals, one tile per 256-thread
@@ -450,6 +448,16 @@ __device__ __forceinline__ void eval_hybrid_body(const ClauseView& cv, const Loo
     // zero word for lanes that need no LDS word (past every word the fill writes)
     const uint32_t zslot = (lds_words + 3) / 4 * 4;
     if (threadIdx.x == 0) s_A[zslot] = 0u;
+    // EV_SCATTER: the owner epoch and the bounds of this workgroup's last run do not depend on
+    // the evaluation; loaded with the window (the fill's wait covers them), they cost the
+    // scatter no round trip of its own
+    uint32_t sc_epoch = 0, sc_a0 = 0, sc_a1 = 0;
+    if constexpr (MODE == EV_SCATTER) {
+        const uint32_t rl = (blockIdx.x + 1) * (b.n_runs / gridDim.x) - 1;
+        sc_epoch = b.state->round_next;
+        sc_a0 = b.run_t0[rl];
+        sc_a1 = b.run_t0[rl + 1];
+    }
     fill(wb);
     const uint32_t a_lo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)b.A);
     const uint32_t a_hi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)b.A >> 32));
@@ -670,8 +678,10 @@ __device__ __forceinline__ void eval_hybrid_body(const ClauseView& cv, const Loo
         else if (kl) run_chunks_t(std::false_type{}, std::false_type{}, std::true_type{}, gbeg, gend, pt);
         else run_chunks_t(std::false_type{}, std::false_type{}, std::false_type{}, gbeg, gend, pt);
     };
+    uint32_t pt_last = t0;  // first tile of the last pass: s_tcnt holds the counts of [pt_last, t1)
     for (uint32_t pt = t0; pt < t1; pt += HYB_MAX_TILES) {
         const uint32_t pe = min(t1, pt + HYB_MAX_TILES);
+        pt_last = pt;
         if (threadIdx.x < HYB_MAX_TILES) s_tcnt[threadIdx.x] = 0;
         __syncthreads();  // also publishes the LDS fill
       // segments of tiles with one window (and one bit 31: slot K-1 in LDS only); the LDS is
@@ -705,10 +715,17 @@ __device__ __forceinline__ void eval_hybrid_body(const ClauseView& cv, const Loo
         // lists it has just written (L2-warm) and with the window's LDS, instead of a
         // separate k_bscatter launch; the reduce then runs in k_bresolve (pre-reduce epoch).
         __syncthreads();  // every wave is done with the window; the lists and counts are visible
+        // A run whose tiles lie in the last pass takes its tile counts from s_tcnt (this
+        // workgroup wrote the global counts from it a few lines up); at one run per workgroup
+        // that is every run, and with the bounds read at kernel start the scatter's first global
+        // loads are its entries.  Runs of earlier passes read their counts back from tile_cnt.
         const ScatterLds L = carve_scatter_lds(s_A);
         const uint32_t rpw = b.n_runs / gridDim.x;
         for (uint32_t r = blockIdx.x * rpw; r < (blockIdx.x + 1) * rpw; ++r) {
-            scatter_run<K>(cv, b, b.stage[0], r, b.state->round_next, L);
+            const bool lastr = r + 1 == (blockIdx.x + 1) * rpw;
+            const uint32_t a0 = lastr ? sc_a0 : b.run_t0[r], a1 = lastr ? sc_a1 : b.run_t0[r + 1];
+            scatter_run<K>(cv, b, b.stage[0], r, a0, a1 - a0, a0 >= pt_last ? s_tcnt + (a0 - pt_last) : nullptr, sc_epoch,
+                           L);
             __syncthreads();  // (the LDS is reused by the next run)
         }
     }
@@ -1026,7 +1043,11 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_collect(ClauseView cv, LoopBuf
 // ------------------------------------------------------------------------------------
 // Violated count + loop state (mode 0) or standalone count (mode 1), by one 1024-thread
 // workgroup: k_reduce, or the extra workgroup of k_bscatter (fused reduce).
-__device__ void reduce_body(const LoopBuffers& b, int mode) {
+// (mode 0) t_from, acc0, first0: the caller has counted the tiles below t_from already -- this
+// thread's share of them in acc0 / first0, as the loop below would have -- from loads it issued
+// ahead of other work (k_bresolve).
+__device__ void reduce_body(const LoopBuffers& b, int mode, uint32_t t_from = 0, unsigned long long acc0 = 0,
+                            uint32_t first0 = ~0u) {
     DevState* st = b.state;
     const unsigned long long reduce_t0 = wall_now();
     __shared__ unsigned long long s_sum;
@@ -1039,10 +1060,10 @@ __device__ void reduce_body(const LoopBuffers& b, int mode) {
         uint4* cv4 = reinterpret_cast<uint4*>(b.cover);  // n_words * 32 bytes
         for (uint32_t i = threadIdx.x; i < b.n_words * 2; i += blockDim.x) cv4[i] = make_uint4(0, 0, 0, 0);
     }
-    unsigned long long acc = 0;
-    uint32_t first = ~0u;
+    unsigned long long acc = acc0;
+    uint32_t first = first0;
     // (mode 1, the standalone count: this rank's tiles, the only ones it evaluates)
-    const uint32_t t_lo = mode == 1 ? b.own_begin : 0u, t_hi = mode == 1 ? b.own_end : b.n_tiles;
+    const uint32_t t_lo = mode == 1 ? b.own_begin : t_from, t_hi = mode == 1 ? b.own_end : b.n_tiles;
     for (uint32_t t = t_lo + threadIdx.x; t < t_hi; t += blockDim.x) {
         const uint32_t cnt = b.tile_cnt[t];
         acc += cnt;
@@ -1555,12 +1576,23 @@ __device__ __forceinline__ uint32_t bucket_of(const LoopBuffers& b, uint32_t v, 
     return q;
 }
 
-// Run-local entry index f -> (tile of the run, index in that tile); pre = prefix of the
-// run's tile counts (<= RUN_TILES_MAX + 1 entries, in LDS).
-__device__ __forceinline__ uint32_t run_tile_of(const uint32_t* pre, uint32_t nt, uint32_t f) {
-    uint32_t tt = 0;
-    while (tt + 1 < nt && pre[tt + 1] <= f) ++tt;
-    return tt;
+// Run-local entry indices f[0 .. U) -> tile of the run (the last one that starts at or before f).
+// pre = prefix of the run's tile counts in LDS, RUN_TILES_MAX + 1 entries, those past the run's
+// last tile equal to its entry count.  A binary search of fixed depth, the U searches step by
+// step side by side: log2(RUN_TILES_MAX) LDS round trips for all of them, where a linear walk
+// is one dependent round trip per tile and entry.
+template <int U>
+__device__ __forceinline__ void run_tiles_of(const uint32_t* pre, const uint32_t* f, uint32_t* tt) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) tt[u] = 0;
+#pragma unroll
+    for (uint32_t step = RUN_TILES_MAX / 2; step; step >>= 1) {
+        uint32_t p[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) p[u] = pre[tt[u] + step];
+#pragma unroll
+        for (int u = 0; u < U; ++u) tt[u] += p[u] <= f[u] ? step : 0u;
+    }
 }
 
 // Loops below are unrolled by BKT_UNROLL independent items per thread so that their global
@@ -1569,51 +1601,58 @@ __device__ __forceinline__ uint32_t run_tile_of(const uint32_t* pre, uint32_t nt
 // between the phases of a kernel instead of being re-read.
 constexpr int BKT_UNROLL = 4;
 
-// Tile counts of run r -> LDS prefix (nt + 1 entries); returns the run's entry count.
-__device__ __forceinline__ uint32_t run_prefix(const LoopBuffers& b, uint32_t t0, uint32_t nt, uint32_t* s_tc,
-                                               uint32_t* s_pre) {
-    if (threadIdx.x < nt) s_tc[threadIdx.x] = b.tile_cnt[t0 + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t acc = 0;
-        for (uint32_t tt = 0; tt < nt; ++tt) { s_pre[tt] = acc; acc += s_tc[tt]; }
-        s_pre[nt] = acc;
+// Tile counts of a run (tc[0 .. nt), global or LDS; nt <= RUN_TILES_MAX) -> the prefix of
+// run_tiles_of in LDS and in the run's record (rec), by a scan in the first wave: one barrier,
+// no serial pass.  Returns the run's entry count.
+__device__ __forceinline__ uint32_t run_prefix(const uint32_t* tc, uint32_t nt, uint32_t* s_pre, uint32_t* rec) {
+    static_assert((RUN_TILES_MAX & (RUN_TILES_MAX - 1)) == 0 && RUN_TILES_MAX <= 16, "a row of the wave, a power of two");
+    if (threadIdx.x < 64) {  // (the whole first wave: wave_incl_add)
+        const uint32_t incl = wave_incl_add(threadIdx.x < nt ? tc[threadIdx.x] : 0u);
+        if (threadIdx.x < RUN_TILES_MAX) {
+            s_pre[threadIdx.x + 1] = incl;
+            rec[RUN_REC_PRE + 1 + threadIdx.x] = incl;
+        }
+        if (threadIdx.x == 0) {
+            s_pre[0] = 0;
+            rec[RUN_REC_PRE] = 0;
+        }
     }
     __syncthreads();
-    return s_pre[nt];
+    return s_pre[RUN_TILES_MAX];
 }
 
 // Load the U entries f0 + u * blockDim.x of the run (ok[u] = exists; tt/idx = its tile / slot).
 template <int K, int U>
-__device__ __forceinline__ void load_run_entries(const uint32_t* list, uint32_t t0, uint32_t nt, const uint32_t* s_pre,
-                                                 uint32_t E, uint32_t f0, Ent<K>* e, bool* ok, uint32_t* tt,
-                                                 uint32_t* idx) {
+__device__ __forceinline__ void load_run_entries(const uint32_t* list, uint32_t t0, const uint32_t* s_pre, uint32_t E,
+                                                 uint32_t f0, Ent<K>* e, bool* ok, uint32_t* tt, uint32_t* idx) {
     constexpr int S = Ent<K>::S;
+    uint32_t f[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) f[u] = f0 + u * blockDim.x;
+    run_tiles_of<U>(s_pre, f, tt);
+#pragma unroll
+    for (int u = 0; u < U; ++u) idx[u] = f[u] - s_pre[tt[u]];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const uint32_t f = f0 + u * blockDim.x;
-        ok[u] = f < E;
-        if (ok[u]) {
-            tt[u] = run_tile_of(s_pre, nt, f);
-            idx[u] = f - s_pre[tt[u]];
-            load_ent<K>(e[u], list + ((uint64_t)(t0 + tt[u]) * TILE + idx[u]) * S);
-        }
+        ok[u] = f[u] < E;
+        if (ok[u]) load_ent<K>(e[u], list + ((uint64_t)(t0 + tt[u]) * TILE + idx[u]) * S);
     }
 }
 
-// Bucket scatter of run r (tiles run_t0[r] .. run_t0[r+1]) by the whole workgroup
+// Bucket scatter of run r (tiles t0 .. t0 + nt = run_t0[r] .. run_t0[r+1]) by the whole workgroup
 // (BSC_THREADS threads): the pairs of its claims grouped by variable bucket into the run's
-// pair area, the segment table column runtab[.][r], hot claims into owner[] under `epoch`.
+// pair area, the segment table column runtab[.][r], hot claims into owner[] under `epoch`, and
+// the run's record for k_bjoin.  lds_tc: the run's tile counts when the caller holds them in
+// LDS (the fused evaluation), nullptr: read from tile_cnt.
 // Every thread must call it (workgroup barriers inside).
 template <int K>
-__device__ void scatter_run(const ClauseView& cv, const LoopBuffers& b, uint32_t* list, uint32_t r, uint32_t epoch,
-                            const ScatterLds& L) {
+__device__ void scatter_run(const ClauseView& cv, const LoopBuffers& b, uint32_t* list, uint32_t r, uint32_t t0,
+                            uint32_t nt, const uint32_t* lds_tc, uint32_t epoch, const ScatterLds& L) {
     constexpr int S = Ent<K>::S;
     constexpr int U = BKT_UNROLL;
-    const uint32_t t0 = b.run_t0[r], nt = b.run_t0[r + 1] - t0;
     uint32_t* s_hist = L.hist;
-    uint32_t* s_tc = L.tc;
     uint32_t* s_pre = L.pre;
+    uint32_t* rec = b.run_rec + (uint64_t)r * RUN_REC_WORDS;
     uint32_t* s_wsum = L.wsum;
     unsigned long long* s_pairs = L.pairs;
     HotTable ht{L.hk, L.hv};
@@ -1621,7 +1660,7 @@ __device__ void scatter_run(const ClauseView& cv, const LoopBuffers& b, uint32_t
     if (hot) ht.init();
     const uint32_t nb = b.n_bkt;
     for (uint32_t i = threadIdx.x; i < nb; i += blockDim.x) s_hist[i] = 0;
-    const uint32_t E = run_prefix(b, t0, nt, s_tc, s_pre);
+    const uint32_t E = run_prefix(lds_tc ? lds_tc : b.tile_cnt + t0, nt, s_pre, rec);
     const bool single = E <= blockDim.x * U;
     const unsigned long long keyhi = (unsigned long long)(~epoch) << 32;
     Ent<K> e[U];
@@ -1635,7 +1674,7 @@ __device__ void scatter_run(const ClauseView& cv, const LoopBuffers& b, uint32_t
     // pass 1: bucket histogram (variables only: it runs while the clause-id loads are in
     // flight), clause ids (written back), hot claims
     for (uint32_t f0 = threadIdx.x; f0 < E; f0 += blockDim.x * U) {
-        load_run_entries<K, U>(list, t0, nt, s_pre, E, f0, e, ok, tts, idx);
+        load_run_entries<K, U>(list, t0, s_pre, E, f0, e, ok, tts, idx);
         // raw entries from the evaluation: packed ids are unpacked here (ALU); without packed
         // ids the perm loads are issued first and land while the histogram runs
         uint32_t id[U];
@@ -1691,11 +1730,7 @@ __device__ void scatter_run(const ClauseView& cv, const LoopBuffers& b, uint32_t
     const uint32_t b0 = min(nb, threadIdx.x * per), b1 = min(nb, b0 + per);
     uint32_t sum = 0;
     for (uint32_t k = b0; k < b1; ++k) sum += s_hist[k];
-    uint32_t incl = sum;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += y;
-    }
+    const uint32_t incl = wave_incl_add(sum);  // (every lane is here)
     if (lane == 63) s_wsum[wave] = incl;
     __syncthreads();
     uint32_t wbase = 0, total = 0;
@@ -1710,7 +1745,10 @@ __device__ void scatter_run(const ClauseView& cv, const LoopBuffers& b, uint32_t
         s_hist[k] = run;
         run += c;
     }
-    if (threadIdx.x == 0) b.run_pairs[r] = total;
+    if (threadIdx.x == 0) {
+        rec[RUN_REC_E] = E;
+        rec[RUN_REC_NP] = total;
+    }
     __syncthreads();
     // pass 2: pairs grouped by bucket, staged in LDS when they fit so that the run's area is
     // written with whole-line stores
@@ -1739,13 +1777,17 @@ __device__ void scatter_run(const ClauseView& cv, const LoopBuffers& b, uint32_t
         emit();  // this thread's entries are still in registers
     } else {
         for (uint32_t f0 = threadIdx.x; f0 < E; f0 += blockDim.x * U) {
-            load_run_entries<K, U>(list, t0, nt, s_pre, E, f0, e, ok, tts, idx);
+            load_run_entries<K, U>(list, t0, s_pre, E, f0, e, ok, tts, idx);
             emit();
         }
     }
     if (staged) {
         __syncthreads();
-        for (uint32_t i = threadIdx.x; i < total; i += blockDim.x) gpr[i] = s_pairs[i];
+        // two pairs per lane (16-byte accesses: the area and the staging buffer are 16-byte aligned)
+        ulonglong2* g2 = reinterpret_cast<ulonglong2*>(gpr);
+        const ulonglong2* s2 = reinterpret_cast<const ulonglong2*>(s_pairs);
+        for (uint32_t i = threadIdx.x; i < total / 2; i += blockDim.x) g2[i] = s2[i];
+        if ((total & 1u) && threadIdx.x == 0) gpr[total - 1] = s_pairs[total - 1];
     }
 }
 
@@ -1762,11 +1804,12 @@ __global__ __launch_bounds__(BSC_THREADS) void k_bscatter(ClauseView cv, LoopBuf
     __shared__ uint32_t s_hist[BKT_MAX];
     __shared__ uint32_t s_hk[HOT_SLOTS];
     __shared__ unsigned long long s_hv[HOT_SLOTS];
-    __shared__ uint32_t s_tc[RUN_TILES_MAX], s_pre[RUN_TILES_MAX + 4];
+    __shared__ uint32_t s_pre[RUN_TILES_MAX + 4];
     __shared__ uint32_t s_wsum[BSC_THREADS / 64];
-    extern __shared__ unsigned long long s_pairs[];  // BKT_STAGE pairs
-    const ScatterLds L{s_hist, s_hk, s_hv, s_tc, s_pre, s_wsum, s_pairs};
-    scatter_run<K>(cv, b, list, blockIdx.x, pre_reduce ? st->round_next : st->round_base, L);
+    extern __shared__ __attribute__((aligned(16))) unsigned long long s_pairs[];  // BKT_STAGE pairs
+    const ScatterLds L{s_hist, s_hk, s_hv, s_pre, s_wsum, s_pairs};
+    const uint32_t r = blockIdx.x, t0 = b.run_t0[r];
+    scatter_run<K>(cv, b, list, r, t0, b.run_t0[r + 1] - t0, nullptr, pre_reduce ? st->round_next : st->round_base, L);
 }
 
 // Workgroup per bucket.  The run table column is processed in batches of BKT_RUN_BATCH runs:
@@ -1782,6 +1825,9 @@ constexpr int BRS_THREADS = 512;
 // per CU; 150 VGPRs, one workgroup per CU), or 16 (8192 pairs; two workgroups per CU) when
 // there are more buckets than CUs.
 constexpr int BRS_UNROLL_WIDE = 20, BRS_UNROLL_NARROW = 16, BRS_UNROLL_DEEP = 8;
+// Tile counts per thread that the reducing workgroup of k_bresolve loads ahead of its bucket
+// (8 x 512 threads: the tiles of 16.7M clauses; the reduce loads the rest as k_reduce does).
+constexpr int BRS_RED_PRE = 8;
 constexpr int BRS_THREADS_DEEP = 1024;
 constexpr uint32_t BRS_DEEP_LDS = 48u << 10;  // minima above this: the deep variant
 
@@ -1874,8 +1920,21 @@ __global__ __launch_bounds__(T, (U <= BRS_UNROLL_NARROW && T <= 512) ? 2 : 1) vo
                                                                                               uint32_t run_cap,
                                                                                               int fused_reduce) {
     if (!fused_reduce && !b.state->active) return;
+    // The reducing workgroup issues the loads of its first BRS_RED_PRE * T tile counts here, so
+    // that they land while its bucket is resolved and the reduce behind the bucket starts from
+    // registers: the workgroup ends with the others instead of several round trips after them.
+    // (The evaluation wrote the counts; nothing in this kernel writes them.)
+    const bool reducing = fused_reduce && blockIdx.x == 0;  // (no extra workgroup: every CU may hold a bucket)
+    uint32_t rc[BRS_RED_PRE];
+    if (reducing) {
+#pragma unroll
+        for (int u = 0; u < BRS_RED_PRE; ++u) {
+            const uint32_t t = u * T + threadIdx.x;
+            rc[u] = t < b.n_tiles ? b.tile_cnt[t] : 0u;
+        }
+    }
     resolve_bucket<U, T>(b, run_cap);
-    if (fused_reduce && blockIdx.x == 0) {  // (no extra workgroup: every CU may hold a bucket)
+    if (reducing) {
         __syncthreads();
         if (eval_gate_closed(b.state)) {
             if (threadIdx.x == 0) {
@@ -1883,7 +1942,14 @@ __global__ __launch_bounds__(T, (U <= BRS_UNROLL_NARROW && T <= 512) ? 2 : 1) vo
                 if (b.A_best) b.state->improved = 0;  // (as k_reduce)
             }
         } else {
-            reduce_body(b, 0);
+            unsigned long long acc = 0;
+            uint32_t first = ~0u;
+#pragma unroll
+            for (int u = BRS_RED_PRE - 1; u >= 0; --u) {
+                acc += rc[u];
+                if (rc[u]) first = u * T + threadIdx.x;
+            }
+            reduce_body(b, 0, BRS_RED_PRE * T, acc, first);
         }
     }
 }
@@ -1972,42 +2038,54 @@ __global__ __launch_bounds__(BJN_THREADS) void k_bjoin(ClauseView cv, LoopBuffer
     constexpr int S = Ent<K>::S;
     constexpr int U = K <= 4 ? 2 * BKT_UNROLL : BKT_UNROLL;
     const uint32_t r = blockIdx.x;
-    // the loop state with the run's bounds and pair count (one round trip)
+    // the loop state with the run's bounds and its record from the scatter -- entries, pairs,
+    // prefix of the tile counts -- in one round trip; the entry and pair loads follow at once
+    const uint32_t* rec = b.run_rec + (uint64_t)r * RUN_REC_WORDS;
     const uint32_t t0 = b.run_t0[r], nt = b.run_t0[r + 1] - t0;
-    const uint32_t np = b.run_pairs[r];
+    const uint32_t E = rec[RUN_REC_E], np = rec[RUN_REC_NP];
+    const uint32_t pre_w = threadIdx.x <= RUN_TILES_MAX ? rec[RUN_REC_PRE + threadIdx.x] : 0u;
     const uint32_t active = st->active, stamp = st->stamp, rbase = st->round_base;
     spec_fence();
     if (!active) return;
+    // The pairs two per load: the run's area is contiguous and 16-byte aligned, and it holds an
+    // even number of slots, so the load of an odd last pair stays inside it (the slot after it is
+    // stale: the marking loop skips it).  The first sweep's loads are issued here, ahead of the
+    // LDS set-up and its barrier, and nothing touches their registers before the marking loop.
+    const ulonglong2* pr2 = reinterpret_cast<const ulonglong2*>(b.pairs + (uint64_t)r * b.run_tiles * TILE * K);
+    constexpr int PU = 8;  // pair couples per thread per sweep (~3 pairs per clause: one sweep at 10M clauses)
+    ulonglong2 x[PU];
+    auto load_pairs = [&](uint32_t i0) {
+#pragma unroll
+        for (int u = 0; u < PU; ++u) {
+            const uint32_t i = i0 + u * blockDim.x;
+            if (2 * i < np) x[u] = pr2[i];
+        }
+    };
+    load_pairs(threadIdx.x);
     extern __shared__ uint32_t s_lost[];  // one byte per entry slot of the run's tiles
-    __shared__ uint32_t s_tc[RUN_TILES_MAX], s_pre[RUN_TILES_MAX + 1], s_keep[RUN_TILES_MAX],
-        s_join[RUN_TILES_MAX], s_mis0[RUN_TILES_MAX], s_base[RUN_TILES_MAX];
-    __shared__ unsigned long long s_lits[RUN_TILES_MAX];
+    __shared__ uint32_t s_pre[RUN_TILES_MAX + 1], s_keep[RUN_TILES_MAX], s_join[RUN_TILES_MAX], s_base[RUN_TILES_MAX];
     for (uint32_t i = threadIdx.x; i < nt * TILE / 4; i += blockDim.x) s_lost[i] = 0;
     if (threadIdx.x < nt) {
         s_keep[threadIdx.x] = 0;
         s_join[threadIdx.x] = 0;
-        s_lits[threadIdx.x] = 0;
-        s_mis0[threadIdx.x] = b.mis_cnt[t0 + threadIdx.x];
     }
-    const uint32_t E = run_prefix(b, t0, nt, s_tc, s_pre);
+    if (threadIdx.x <= RUN_TILES_MAX) s_pre[threadIdx.x] = pre_w;
+    __syncthreads();
     const bool single = E <= blockDim.x * U;
     Ent<K> e[U];
     bool ok[U];
     uint32_t tts[U], idx[U];
-    if (single) load_run_entries<K, U>(in, t0, nt, s_pre, E, threadIdx.x, e, ok, tts, idx);
+    if (single) load_run_entries<K, U>(in, t0, s_pre, E, threadIdx.x, e, ok, tts, idx);
     uint8_t* lost = reinterpret_cast<uint8_t*>(s_lost);
-    const unsigned long long* pr = b.pairs + (uint64_t)r * b.run_tiles * TILE * K;
-    constexpr int PU = 16;  // pairs per thread per sweep (~3 per clause: one sweep at 10M clauses)
-    for (uint32_t i0 = threadIdx.x; i0 < np; i0 += blockDim.x * PU) {
-        unsigned long long x[PU];
+    for (uint32_t i0 = threadIdx.x; 2 * i0 < np;) {
 #pragma unroll
         for (int u = 0; u < PU; ++u) {
-            const uint32_t i = i0 + u * blockDim.x;
-            x[u] = i < np ? pr[i] : 0ull;
+            const uint32_t i = 2 * (i0 + u * blockDim.x);
+            if (i < np && (x[u].x & PAIR_LOSE)) lost[(x[u].x >> 15) & 0xFFFFu] = 1;
+            if (i + 1 < np && (x[u].y & PAIR_LOSE)) lost[(x[u].y >> 15) & 0xFFFFu] = 1;
         }
-#pragma unroll
-        for (int u = 0; u < PU; ++u)
-            if (x[u] & PAIR_LOSE) lost[(x[u] >> 15) & 0xFFFFu] = 1;
+        i0 += blockDim.x * PU;
+        if (2 * i0 < np) load_pairs(i0);
     }
     __syncthreads();
     const bool hot = cv.n_hot != 0;
@@ -2029,8 +2107,7 @@ __global__ __launch_bounds__(BJN_THREADS) void k_bjoin(ClauseView cv, LoopBuffer
             if (own) {
 #pragma unroll
                 for (int j = 0; j < K; ++j) b.cover[lit_var(e[u].w[1 + j])] = (uint8_t)stamp;
-                b.mis[(uint64_t)tile * TILE + s_mis0[tt] + atomicAdd(&s_join[tt], 1u)] = e[u].w[0];
-                atomicAdd(&s_lits[tt], (unsigned long long)K);
+                b.mis[(uint64_t)tile * TILE + atomicAdd(&s_join[tt], 1u)] = e[u].w[0];
             } else {
                 store_ent<K>(out + ((uint64_t)tile * TILE + atomicAdd(&s_keep[tt], 1u)) * S, e[u]);
             }
@@ -2040,7 +2117,7 @@ __global__ __launch_bounds__(BJN_THREADS) void k_bjoin(ClauseView cv, LoopBuffer
         decide();
     } else {
         for (uint32_t f0 = threadIdx.x; f0 < E; f0 += blockDim.x * U) {
-            load_run_entries<K, U>(in, t0, nt, s_pre, E, f0, e, ok, tts, idx);
+            load_run_entries<K, U>(in, t0, s_pre, E, f0, e, ok, tts, idx);
             decide();
         }
     }
@@ -2049,10 +2126,14 @@ __global__ __launch_bounds__(BJN_THREADS) void k_bjoin(ClauseView cv, LoopBuffer
         const uint32_t tt = threadIdx.x, tile = t0 + tt, kept = s_keep[tt];
         if (last && kept) s_base[tt] = atomicAdd(&st->left_cnt, kept);
         b.tile_cnt[tile] = last ? 0u : kept;
-        b.mis_cnt[tile] = s_mis0[tt] + s_join[tt];
+        // Round 0 is the first to add to the tile's MIS list: mis_cnt is 0 here.  Whatever fills
+        // the lists of an active iteration -- every evaluation kernel for its own tiles, k_collect
+        // for the other ranks' -- zeroes it with the tile's count, and nothing between them and
+        // this kernel writes it, so it is not read back.
+        b.mis_cnt[tile] = s_join[tt];
         if (s_join[tt]) {
             atomicAdd(&b.tile_stats[2 * tile], (unsigned long long)s_join[tt]);
-            atomicAdd(&b.tile_stats[2 * tile + 1], s_lits[tt]);
+            atomicAdd(&b.tile_stats[2 * tile + 1], (unsigned long long)K * s_join[tt]);  // (fixed width: K literals each)
         }
     }
     if (last) {

@@ -430,6 +430,9 @@ Knobs read_knobs() {
     k.packed_ids = on("ALLL_PACKED_IDS", true);  // 0 keeps positions + perm
     k.eval_nt = tri("ALLL_EVAL_NT");
     k.debug_occupancy = getenv("ALLL_DEBUG_OCCUPANCY") != nullptr;
+    // tests: plan and launch as on a device of fewer compute units (one or two evaluation
+    // workgroups own many tiles each: several runs per workgroup, several tile-count passes)
+    if (const char* e = getenv("ALLL_PLAN_CUS")) k.plan_cus = (uint32_t)std::max(0, atoi(e));
     return k;
 }
 

@@ -34,6 +34,7 @@ struct Knobs {
     bool packed_ids = true;             // ALLL_PACKED_IDS
     int eval_nt = -1;                   // ALLL_EVAL_NT: 0 / 1, -1 unset
     bool debug_occupancy = false;       // ALLL_DEBUG_OCCUPANCY
+    uint32_t plan_cus = 0;              // ALLL_PLAN_CUS: >= 1, 0 unset (the device's compute units)
 };
 Knobs read_knobs();
 

@@ -1027,7 +1027,7 @@ int alloc_round0(alll_ctx* c, const Layout& l) {
     if ((rc = upload(c, &b.run_t0, l.run_t0, "run table"))) return rc;
     const size_t run_cap = (size_t)b.run_tiles * TILE * l.fixed_k;
     if ((rc = dalloc(c, &b.pairs, (size_t)b.n_runs * run_cap)) || (rc = dalloc(c, &b.runtab, (size_t)b.n_bkt * b.n_runs)) ||
-        (rc = dalloc(c, &b.run_pairs, b.n_runs)))
+        (rc = dalloc(c, &b.run_rec, (size_t)b.n_runs * RUN_REC_WORDS)))  // (line-aligned: records are one line)
         return rc;
     c->bucket_min_u = l.bucket_min_u;
     return ALLL_OK;
@@ -1128,6 +1128,7 @@ int alll_create(const alll_problem* prob, const alll_options* opt_in, alll_ctx**
     alll_ctx* c = nullptr;
     if ((rc = open_device(opt, &c))) return rc;
     auto bail = [&](int rc) { alll_destroy(c); return rc; };
+    if (kn.plan_cus) c->n_cu = std::min(c->n_cu, (int)std::min<uint32_t>(kn.plan_cus, 1u << 20));  // (ALLL_PLAN_CUS: tests)
     if ((rc = plan_buckets(*prob, opt, kn, (uint32_t)c->n_cu, lay))) return bail(fail(rc, "%s", lay.err.c_str()));
     set_shape(c, opt, kn, lay);
     if ((rc = alloc_round_robin(c, lay)) || (rc = alloc_streaming(c, opt, lay)) || (rc = alloc_loop(c, lay)) ||
