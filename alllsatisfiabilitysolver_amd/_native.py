@@ -73,6 +73,7 @@ EXPORTED = [
     "alll_pinned_propagate", "alll_propagate_pins", "alll_get_var_thresholds",
     "alll_group_propagate_pins", "alll_group_get_var_thresholds",
     "alll_batch_propagate_pins", "alll_batch_get_var_thresholds",
+    "alll_pinned_scores", "alll_var_scores", "alll_group_var_scores",
 ]
 
 
@@ -152,6 +153,19 @@ class PropagateResult(ctypes.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class SplitResult(ctypes.Structure):
+    _fields_ = [
+        ("score_pos", ctypes.c_uint64),
+        ("score_neg", ctypes.c_uint64),
+        ("n_open", ctypes.c_uint64),
+        ("var", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
 
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -245,6 +259,10 @@ _SIGS = {
     "alll_group_get_var_thresholds": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
     "alll_batch_propagate_pins": ([_vp, ctypes.c_uint64, ctypes.POINTER(PropagateResult)], ctypes.c_int),
     "alll_batch_get_var_thresholds": ([_vp, ctypes.c_uint64, _u32p, ctypes.c_uint64], ctypes.c_int),
+    "alll_pinned_scores": ([ctypes.POINTER(Problem), _u32p, ctypes.c_uint64, _u64p, ctypes.POINTER(SplitResult)],
+                           ctypes.c_int),
+    "alll_var_scores": ([_vp, _u64p, ctypes.c_uint64, ctypes.POINTER(SplitResult)], ctypes.c_int),
+    "alll_group_var_scores": ([_vp, ctypes.POINTER(SplitResult), _u64p, ctypes.c_uint64], ctypes.c_int),
 }
 
 _lib = None

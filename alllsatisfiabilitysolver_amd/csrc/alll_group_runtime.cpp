@@ -16,6 +16,7 @@
 #include "alll_group_dev.h"
 #include "alll_propagate.h"
 #include "alll_rt_util.h"
+#include "alll_score.h"
 
 using namespace alll;
 
@@ -335,6 +336,54 @@ int alll_group_propagate_pins(alll_group* g, uint64_t max_rounds, alll_propagate
     }
     HIP_TRY(hipStreamSynchronize(g->stream));
     ctx_assignment_changed(g->ctx);
+    return ALLL_OK;
+}
+
+// Split scores of every item at once: one pass of the context's scoring kernels
+// over the union; the items' scores are then cut out of the union's array, without its word padding.
+int alll_group_var_scores(alll_group* g, alll_split_result* results, uint64_t* scores, uint64_t n_scores) {
+    if (!g || !results) return fail(ALLL_ERR_INVALID_ARG, "var scores: null argument");
+    int rc;
+    if ((rc = ctx_bias_supported(g->ctx))) return rc;
+    const uint32_t n = g->d.n_items;
+    uint64_t want = 0;
+    for (const GroupItem& it : g->items) want += 2ull * it.n_vars;
+    if (scores && n_scores != want)
+        return fail(ALLL_ERR_INVALID_ARG, "var scores: %llu entries for the %llu literals of the items",
+                    (unsigned long long)n_scores, (unsigned long long)want);
+    HIP_TRY(hipSetDevice(g->device));
+    const CtxAccess a = ctx_access(g->ctx);
+    if (!g->d_word_item) {
+        std::vector<uint32_t> word_item(a.b->n_words, 0u);
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t w = 0; w < g->items[i].n_words; ++w) word_item[g->items[i].word_base + w] = i;
+        if ((rc = upload(g, &g->d_word_item, word_item.data(), word_item.size()))) return rc;
+    }
+    PropArgs p{};
+    p.lits = a.cv->lits;
+    p.offs = a.cv->offs;
+    p.m = a.cv->m;
+    p.k = a.cv->k;
+    p.n_vars = a.b->n_vars;
+    p.n_words = a.b->n_words;
+    p.n_items = n;
+    p.thr = const_cast<uint32_t*>(g->d_thr);  // (nullptr: no item has thresholds)
+    p.words = g->d.words;
+    p.wbias = g->d_wbias;
+    p.word_item = g->d_word_item;
+    p.clause_base = g->d.clause_base;
+    std::vector<uint32_t> item_vars(2ull * n);
+    for (uint32_t i = 0; i < n; ++i) {
+        item_vars[2 * i] = g->items[i].var_base;
+        item_vars[2 * i + 1] = g->items[i].n_vars;
+    }
+    std::vector<uint64_t> S;
+    if ((rc = score_drive(p, item_vars, results, scores ? &S : nullptr, g->stream))) return rc;
+    if (scores)
+        for (const GroupItem& it : g->items) {
+            if (it.n_vars) memcpy(scores, S.data() + 2ull * it.var_base, 16ull * it.n_vars);
+            scores += 2ull * it.n_vars;
+        }
     return ALLL_OK;
 }
 

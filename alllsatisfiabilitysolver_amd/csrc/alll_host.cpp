@@ -493,14 +493,16 @@ int alll_biased_initial_assignment(uint64_t seed, uint32_t n_vars, const uint32_
     return ALLL_OK;
 }
 
-// The validation alll_pinned_conflict and alll_pinned_propagate share (`what` opens the message).
-static int pinned_validate(const alll_problem* prob, const uint32_t* thr, uint64_t n, const void* out, const char* what) {
+// The validation alll_pinned_conflict, alll_pinned_propagate and alll_pinned_scores share (`what`
+// opens the message); thr_optional: a null thr is no error, and n is then not looked at.
+static int pinned_validate(const alll_problem* prob, const uint32_t* thr, uint64_t n, const void* out, const char* what,
+                           bool thr_optional = false) {
     const std::string w(what);
-    if (!prob || !out || (!thr && n)) {
+    if (!prob || !out || (!thr && n && !thr_optional)) {
         g_host_err = w + ": null argument";
         return ALLL_ERR_INVALID_ARG;
     }
-    if (n != prob->n_vars) {
+    if (n != prob->n_vars && !(thr_optional && !thr)) {
         g_host_err = w + ": " + std::to_string(n) + " thresholds for " + std::to_string(prob->n_vars) + " variables";
         return ALLL_ERR_INVALID_ARG;
     }
@@ -598,6 +600,48 @@ int alll_pinned_propagate(const alll_problem* prob, uint32_t* thr, uint64_t n, u
         r.n_forced += touched.size();
         r.rounds += 1;
     }
+    *res = r;
+    return ALLL_OK;
+}
+
+// The split scores (include/alll.h): a pass that classifies every clause and counts its free
+// occurrences, then adds the clause's weight to each of them; the arg-max keeps the lowest variable.
+int alll_pinned_scores(const alll_problem* prob, const uint32_t* thr, uint64_t n, uint64_t* scores,
+                       alll_split_result* res) {
+    if (int rc = pinned_validate(prob, thr, n, res, "pinned scores", true)) return rc;
+    const uint64_t m = prob->n_clauses;
+    const uint32_t nv = prob->n_vars;
+    std::vector<uint64_t> S(2 * (size_t)nv, 0);
+    auto is_free = [&](uint32_t l) { return !thr || (thr[l >> 1] != 0u && thr[l >> 1] != 0xFFFFFFFFu); };
+    alll_split_result r{0, 0, 0, nv, 0};
+    for (uint64_t c = 0; c < m; ++c) {
+        bool sat = false;
+        uint32_t f = 0;
+        for (uint64_t j = prob->offsets[c]; j < prob->offsets[c + 1] && !sat; ++j) {
+            const uint32_t l = prob->literals[j];
+            if (is_free(l)) ++f;
+            else sat = thr[l >> 1] == ((l & 1u) ? 0u : 0xFFFFFFFFu);
+        }
+        if (sat) continue;
+        r.n_open += 1;
+        if (!f) continue;
+        const uint64_t w = 1ull << (16 - std::min(f, 16u));
+        for (uint64_t j = prob->offsets[c]; j < prob->offsets[c + 1]; ++j)
+            if (is_free(prob->literals[j])) S[prob->literals[j]] += w;
+    }
+    uint64_t best = 0;
+    for (uint32_t v = 0; v < nv; ++v) {
+        const uint64_t t = S[2 * (size_t)v] + S[2 * (size_t)v + 1];
+        if (t > best) {
+            best = t;
+            r.var = v;
+        }
+    }
+    if (r.var < nv) {
+        r.score_pos = S[2 * (size_t)r.var];
+        r.score_neg = S[2 * (size_t)r.var + 1];
+    }
+    if (scores && nv) memcpy(scores, S.data(), S.size() * sizeof(uint64_t));
     *res = r;
     return ALLL_OK;
 }

@@ -47,6 +47,17 @@ struct PropArgs {
     const uint32_t* clause_base;
 };
 
+// the item of clause c: the last clause base <= c (n_items + 1 ascending bases; empty items share one)
+__device__ __forceinline__ uint32_t prop_clause_item(const uint32_t* clause_base, uint32_t n_items, uint32_t c) {
+    uint32_t lo = 0, hi = n_items;  // clause_base[lo] <= c < clause_base[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (clause_base[mid] <= c) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // Launchers (alll_propagate.hip).  All asynchronous on `s`.
 hipError_t launch_prop_pack(const PropArgs& a, hipStream_t s);
 hipError_t launch_prop_scan(const PropArgs& a, hipStream_t s);

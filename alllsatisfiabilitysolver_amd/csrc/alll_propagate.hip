@@ -51,17 +51,6 @@ __global__ __launch_bounds__(PROP_THREADS) void k_prop_pack(const PropArgs a) {
     a.F0[w] = 0;
 }
 
-// the item of clause c: the last clause base <= c (n_items + 1 ascending bases; empty items share one)
-__device__ __forceinline__ uint32_t prop_clause_item(const PropArgs& a, uint32_t c) {
-    uint32_t lo = 0, hi = a.n_items;  // clause_base[lo] <= c < clause_base[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a.clause_base[mid] <= c) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(PROP_THREADS) void k_prop_scan(const PropArgs a) {
     const uint64_t c = (uint64_t)blockIdx.x * PROP_THREADS + threadIdx.x;
     if (c >= a.m) return;
@@ -95,7 +84,7 @@ __global__ __launch_bounds__(PROP_THREADS) void k_prop_scan(const PropArgs a) {
     }
     if (sat || (n_free && !same)) return;
     if (n_free == 0) {
-        const uint32_t i = a.clause_base ? prop_clause_item(a, (uint32_t)c) : 0u;
+        const uint32_t i = a.clause_base ? prop_clause_item(a.clause_base, a.n_items, (uint32_t)c) : 0u;
         atomicMin(&a.items[i].conflict, (unsigned long long)c);
     } else {
         const uint32_t v = unit >> 1;

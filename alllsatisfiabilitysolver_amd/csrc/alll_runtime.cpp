@@ -25,6 +25,7 @@
 #include "alll_layout.h"
 #include "alll_propagate.h"
 #include "alll_rt_util.h"
+#include "alll_score.h"
 
 using namespace alll;
 
@@ -1431,6 +1432,33 @@ int alll_get_var_thresholds(alll_ctx* c, uint32_t* out, uint64_t n) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (n) HIP_TRY(hipMemcpy(out, c->d_thr, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return ALLL_OK;
+}
+
+// Split scores under the context's thresholds: a pass of its own kernels and
+// scratch on the drained stream; nothing of the context is written.
+int alll_var_scores(alll_ctx* c, uint64_t* scores, uint64_t n_scores, alll_split_result* res) {
+    if (!c || !res) return fail(ALLL_ERR_INVALID_ARG, "var scores: null argument");
+    if (c->grp) return fail(ALLL_ERR_INVALID_ARG, "var scores: the context belongs to a group (alll_group_var_scores)");
+    int rc;
+    if ((rc = bias_supported(c))) return rc;
+    if (scores && n_scores != 2ull * c->n_vars)
+        return fail(ALLL_ERR_INVALID_ARG, "var scores: %llu entries for the %llu literals of %u variables",
+                    (unsigned long long)n_scores, 2ull * c->n_vars, c->n_vars);
+    HIP_TRY(hipSetDevice(c->device));
+    const LoopBuffers& b = c->b;
+    PropArgs a{};
+    a.lits = c->cv.lits;
+    a.offs = c->cv.offs;
+    a.m = c->cv.m;
+    a.k = c->cv.k;
+    a.n_vars = b.n_vars;
+    a.n_words = b.n_words;
+    a.n_items = 1;
+    a.thr = (b.thr && c->d_thr) ? c->d_thr : nullptr;
+    std::vector<uint64_t> S;
+    if ((rc = score_drive(a, {0u, c->n_vars}, res, scores ? &S : nullptr, c->stream))) return rc;
+    if (scores && c->n_vars) memcpy(scores, S.data(), 16ull * c->n_vars);
     return ALLL_OK;
 }
 

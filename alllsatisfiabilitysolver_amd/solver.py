@@ -146,6 +146,26 @@ def propagate_pins(n_vars: int, offsets, literals, thr, max_rounds: int = 0):
     return out, res.as_dict()
 
 
+def var_scores(n_vars: int, offsets, literals, thr=None):
+    """alll_pinned_scores: the split scores under thresholds thr (host-only; None: every variable
+    free).  Returns (scores uint64[2 * n_vars], {"var", "score_pos", "score_neg", "n_open"}): scores[l]
+    is S[l] of include/alll.h, var the free variable with the largest S[2v] + S[2v+1] (the lowest on a
+    tie), n_vars when no open clause holds a free literal."""
+    offs = np.ascontiguousarray(offsets, np.uint64)
+    lits = np.ascontiguousarray(literals, np.uint32)
+    m = max(0, offs.size - 1)
+    prob = N.Problem(int(n_vars), 0, m, _p(offs, _u64p), _p(lits, _u32p))
+    scores = np.zeros(2 * int(n_vars), np.uint64)
+    res = N.SplitResult()
+    if thr is None:
+        t, n = None, 0
+    else:
+        thr = np.ascontiguousarray(thr, np.uint32)
+        t, n = _p(thr, _u32p), thr.size
+    N.check(N.lib().alll_pinned_scores(ctypes.byref(prob), t, n, _p(scores, _u64p), ctypes.byref(res)), "pinned_scores")
+    return scores, res.as_dict()
+
+
 # ----------------------------------------------------------------------------- Solver
 class Solver:
     """Owns one device solver context (alll_ctx).  probabilities: P(x_v = 1) per variable (0 and 1
@@ -236,6 +256,18 @@ class Solver:
         thr = np.zeros(self.n_vars, np.uint32)
         N.check(self._L.alll_get_var_thresholds(self._ctx, _p(thr, _u32p), thr.size), "alll_get_var_thresholds")
         return thr
+
+    def var_scores(self, with_scores: bool = True):
+        """alll_var_scores: the split scores under the solver's current thresholds (none: every
+        variable free), computed on the device.  At any time; nothing of the solver changes.  Returns
+        (scores, split) as var_scores, the host form; with_scores=False: the split record alone."""
+        res = N.SplitResult()
+        if not with_scores:
+            N.check(self._L.alll_var_scores(self._ctx, None, 0, ctypes.byref(res)), "alll_var_scores")
+            return res.as_dict()
+        scores = np.zeros(2 * self.n_vars, np.uint64)
+        N.check(self._L.alll_var_scores(self._ctx, _p(scores, _u64p), scores.size, ctypes.byref(res)), "alll_var_scores")
+        return scores, res.as_dict()
 
     def set_host_exchange(self, exchange):
         """exchange(op, buf: numpy uint8 view, bytes_per_rank_or_total) -> None; see
@@ -600,6 +632,19 @@ class GroupSolver(_ItemSolver):
     def eval_kernel(self) -> str:
         return self._L.alll_group_eval_kernel(self._h).decode()
 
+    def var_scores(self, with_scores: bool = False):
+        """alll_group_var_scores: Solver.var_scores for every item in one pass over the union.  Returns
+        the list of split records, one dict per item in its own variable numbering; with_scores=True:
+        (that list, the list of the items' score arrays)."""
+        res = (N.SplitResult * max(1, self.n_items))()
+        if not with_scores:
+            N.check(self._L.alll_group_var_scores(self._h, res, None, 0), "alll_group_var_scores")
+            return [res[i].as_dict() for i in range(self.n_items)]
+        scores = np.zeros(2 * sum(self.n_vars), np.uint64)
+        N.check(self._L.alll_group_var_scores(self._h, res, _p(scores, _u64p), scores.size), "alll_group_var_scores")
+        cuts = np.cumsum([2 * n for n in self.n_vars])[:-1]
+        return [res[i].as_dict() for i in range(self.n_items)], np.split(scores, cuts)
+
     def epoch_counters(self) -> dict:
         """Solver.epoch_counters of the union."""
         out = np.zeros(4, np.uint64)
@@ -696,6 +741,71 @@ def solve_cubes_propagated(n_vars: int, offsets, literals, cubes, seeds=None, ma
     as well, and the others run, in a second solver of the same kind, under their propagated
     thresholds.  The return value is solve_cubes', the indices are the caller's."""
     return _solve_cubes(n_vars, offsets, literals, cubes, seeds, max_iters, True)
+
+
+def split_cubes(n_vars: int, offsets, literals, depth: int, base=(), device: int = -1):
+    """Grows a tree of cubes from the split scores (the other half of cube-and-conquer), every cube
+    of a level in one pass on the device: a GroupSolver of 2^depth items of the instance, all under
+    cube_thresholds(base) at first.  At every level 0 .. depth the pins of all items are propagated
+    (an item in conflict is a dead leaf and is left alone from then on) and all items scored (an item
+    whose pins satisfy every clause is a leaf); below `depth` every other item i pins its split
+    variable: its preferred literal p is 2 var when score_pos >= score_neg, else 2 var + 1, and it
+    takes p ^ b with b bit depth - 1 - level of i.  Items that share a prefix of bits stay identical,
+    so the leaves are the distinct cubes, in order of their smallest item: depth-first order.
+    Returns the list of leaves {"cube": base + the decisions, "status": "open" | "conflict" |
+    "satisfied", "thr": the propagated thresholds (None for a conflict)}.  1 <= depth <= 10."""
+    if not 1 <= int(depth) <= 10:
+        raise ValueError(f"depth {depth} is not in 1 .. 10")
+    depth, n_items = int(depth), 1 << int(depth)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    literals = np.ascontiguousarray(literals, np.uint32)
+    base = [int(l) for l in base]
+    thr0 = cube_thresholds(n_vars, base)
+    cubes = [list(base) for _ in range(n_items)]
+    status: List[Optional[str]] = [None] * n_items  # (None: live)
+    thrs: List[Optional[np.ndarray]] = [None] * n_items
+    with GroupSolver([(n_vars, offsets, literals)] * n_items, range(1, n_items + 1), device=device) as g:
+        for i in range(n_items):
+            g.set_thresholds(i, thr0)
+        for level in range(depth + 1):
+            for i, r in enumerate(g.propagate_pins()):
+                if status[i] is None and r["status"] == N.PROP_CONFLICT:
+                    status[i] = "conflict"
+            split = g.var_scores()
+            for i in range(n_items):
+                if status[i] is not None:
+                    continue
+                s = split[i]
+                if s["var"] == n_vars:
+                    status[i], thrs[i] = "satisfied", g.thresholds(i)
+                elif level == depth:
+                    status[i], thrs[i] = "open", g.thresholds(i)
+                else:
+                    p = 2 * s["var"] + (0 if s["score_pos"] >= s["score_neg"] else 1)
+                    d = p ^ ((i >> (depth - 1 - level)) & 1)
+                    t = g.thresholds(i)
+                    t[s["var"]] = 0 if d & 1 else 0xFFFFFFFF
+                    g.set_thresholds(i, t)
+                    cubes[i].append(d)
+    leaves, seen = [], set()
+    for i in range(n_items):
+        if tuple(cubes[i]) not in seen:
+            seen.add(tuple(cubes[i]))
+            leaves.append({"cube": cubes[i], "status": status[i], "thr": thrs[i]})
+    return leaves
+
+
+def solve_cubes_split(n_vars: int, offsets, literals, depth: int, base=(), seeds=None, max_iters: int = 0):
+    """A cube portfolio without cubes from the caller: split_cubes, then solve_cubes_propagated on the
+    cubes of the leaves that are not in conflict, in leaf order (seeds: None, or one per such leaf).
+    Returns (leaves, (leaf index, stats, assignment_words)): the winner's index in `leaves`;
+    (leaves, (None, None, None)) when no leaf is left or max_iters capped every one."""
+    leaves = split_cubes(n_vars, offsets, literals, depth, base)
+    live = [j for j, leaf in enumerate(leaves) if leaf["status"] != "conflict"]
+    if not live:
+        return leaves, (None, None, None)
+    win, st, words = solve_cubes_propagated(n_vars, offsets, literals, [leaves[j]["cube"] for j in live], seeds, max_iters)
+    return leaves, ((None, None, None) if win is None else (live[win], st, words))
 
 
 def shard_plan(n_clauses: int, world: int, rank: int):

@@ -300,6 +300,36 @@ typedef struct alll_propagate_result {
 int alll_propagate_pins(alll_ctx* ctx, uint64_t max_rounds, alll_propagate_result* res);
 int alll_get_var_thresholds(alll_ctx* ctx, uint32_t* out, uint64_t n);
 
+/* Split scores: which free variable to pin next.  The literal states under
+ * thresholds thr are those of the propagation above (true, false, free; a bias that is not a pin is
+ * free); without thresholds every variable is free.  For every clause c:
+ *  - c is open when it has no true literal (an empty clause and a falsified clause are open);
+ *  - f(c) is the number of free literal occurrences in c, with multiplicity (x x !y with y pinned 1:
+ *    f = 2; x !x: f = 2);
+ *  - an open clause with f >= 1 adds w(f) = 1 << (16 - min(f, 16)) to S[l] for every free occurrence
+ *    l in it: Jeroslow-Wang weights in integers (32768 for a unit, 8192 for three free literals, 1
+ *    from 16 free literals on).  Integers and + only: the result does not depend on any execution
+ *    order; with fewer than 2^32 literals S[l] < 2^47;
+ *  - a satisfied clause, and an open clause with f = 0, adds nothing.
+ * The scores do not detect conflicts: that is the propagation's job.  After a propagation that ended
+ * in ALLL_PROP_FIXPOINT, var == n_vars holds exactly when n_open == 0: the pins satisfy every clause. */
+typedef struct alll_split_result {
+    uint64_t score_pos;           /* S[2 var]     (0 when var == n_vars) */
+    uint64_t score_neg;           /* S[2 var + 1] */
+    uint64_t n_open;              /* open clauses, falsified and empty ones included */
+    uint32_t var;                 /* argmax over v of T(v) = S[2v] + S[2v+1], T > 0, the lowest v on a tie;
+                                     n_vars when every T is 0 */
+    uint32_t pad;                 /* 0 */
+} alll_split_result;              /* 32 bytes */
+/* The split record of the context under its current thresholds (a context without thresholds: every
+ * variable free), computed on the device; scores: NULL, or n_scores == 2 * n_vars entries that
+ * receive S.  Allowed at any time: the call drains the stream and changes nothing in the context --
+ * assignment, statistics, best record, thresholds and the trajectory afterwards are bit for bit
+ * those of a context that never called it.  It refuses the contexts alll_set_var_thresholds refuses,
+ * with ALLL_ERR_UNSUPPORTED; a null context, a null res, a context that belongs to a group or a
+ * wrong n_scores: ALLL_ERR_INVALID_ARG.  (No reference counterpart.) */
+int alll_var_scores(alll_ctx* ctx, uint64_t* scores, uint64_t n_scores, alll_split_result* res);
+
 /* Introspection of the last iteration (parity tests): violated bitmask of the last eval
  * pass (ceil(n_clauses/64) words) and the MIS picked from it (ascending clause order). */
 int alll_get_violated_mask(alll_ctx* ctx, uint64_t* out, uint64_t n_words);
@@ -488,6 +518,14 @@ int alll_group_set_var_thresholds(alll_group* g, uint64_t item, const uint32_t* 
  * thresholds: ALLL_ERR_INVALID_ARG). */
 int alll_group_propagate_pins(alll_group* g, uint64_t max_rounds, alll_propagate_result* results);
 int alll_group_get_var_thresholds(alll_group* g, uint64_t item, uint32_t* out, uint64_t n);
+/* alll_var_scores over the union, every item at once in one pass (results: n_items entries): item
+ * i's record and scores are exactly those of a context of its own, in its local variable numbering
+ * (var == its n_vars when nothing is left).  scores: NULL, or n_scores == the sum over the items of
+ * 2 * n_vars_i entries, the items one after another in item order (without the union's word
+ * padding).  An item without thresholds has every variable free; whether an item is solved or has
+ * ended does not matter (the scores are a function of clauses and thresholds only).  At any time;
+ * nothing in the group changes. */
+int alll_group_var_scores(alll_group* g, alll_split_result* results, uint64_t* scores, uint64_t n_scores);
 /* alll_track_best / alll_get_best per item (the contract above): switched for every
  * item at once, before the group's first iteration; the same ALLL_ERR_UNSUPPORTED contexts.  Every
  * item keeps its own record, in its local variable numbering and its own pass count, exactly that
@@ -572,6 +610,13 @@ int alll_pinned_conflict(const alll_problem* prob, const uint32_t* thr, uint64_t
  * alll_pinned_conflict reports the same clause. */
 int alll_pinned_propagate(const alll_problem* prob, uint32_t* thr, uint64_t n, uint64_t max_rounds,
                           alll_propagate_result* res);
+
+/* The split scores of alll_var_scores on the host (the semantics above) under thresholds thr (n ==
+ * n_vars entries; thr == NULL: every variable free, n is not looked at).  scores: NULL, or 2 * n_vars
+ * entries that receive S.  Validation and error codes are those of alll_pinned_conflict (but for
+ * the null thr); nothing is written on an error. */
+int alll_pinned_scores(const alll_problem* prob, const uint32_t* thr, uint64_t n, uint64_t* scores,
+                       alll_split_result* res);
 
 /* The reference's own initial assignment (VariablesArray.h:23-34) in the reference-RNG mode
  * (ALLL_FLAG_REFERENCE_RNG): `rd_state` is the random_device stand-in's state
