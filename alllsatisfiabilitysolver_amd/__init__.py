@@ -8,6 +8,7 @@ from ._native import (AlllError, PROP_CONFLICT, PROP_FIXPOINT, PROP_NONE, PROP_R
 from .solver import (BatchSolver, Clause, GroupSolver, SATInstance, Solver, Statistics, VariablesArray,  # noqa: F401
                      batch_fits, solve_portfolio, solve_cubes, solve_cubes_propagated, cube_thresholds, pinned_conflict, propagate_pins, var_thresholds,
                      biased_initial_assignment, var_scores, split_cubes, solve_cubes_split,
+                     residual_instance, lift_assignment, solve_cubes_residual,
                      assignment_digest, comm_unique_id, device_count, generate_ksat, generate_mixed, gloo_exchange,
                      parse_dimacs,
                      read_dimacs, shard_plan, plan_multi_gpu)

@@ -74,6 +74,7 @@ EXPORTED = [
     "alll_group_propagate_pins", "alll_group_get_var_thresholds",
     "alll_batch_propagate_pins", "alll_batch_get_var_thresholds",
     "alll_pinned_scores", "alll_var_scores", "alll_group_var_scores",
+    "alll_pinned_residual", "alll_residual", "alll_group_residual",
 ]
 
 
@@ -161,6 +162,20 @@ class SplitResult(ctypes.Structure):
         ("score_neg", ctypes.c_uint64),
         ("n_open", ctypes.c_uint64),
         ("var", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+class ResidualResult(ctypes.Structure):
+    _fields_ = [
+        ("n_clauses", ctypes.c_uint64),
+        ("n_literals", ctypes.c_uint64),
+        ("n_falsified", ctypes.c_uint64),
+        ("first_falsified", ctypes.c_uint64),
+        ("n_vars", ctypes.c_uint32),
         ("pad", ctypes.c_uint32),
     ]
 
@@ -263,6 +278,10 @@ _SIGS = {
                            ctypes.c_int),
     "alll_var_scores": ([_vp, _u64p, ctypes.c_uint64, ctypes.POINTER(SplitResult)], ctypes.c_int),
     "alll_group_var_scores": ([_vp, ctypes.POINTER(SplitResult), _u64p, ctypes.c_uint64], ctypes.c_int),
+    "alll_pinned_residual": ([ctypes.POINTER(Problem), _u32p, ctypes.c_uint64, ctypes.POINTER(ResidualResult), _u64p, _u32p,
+                              _u32p, _u64p, _u32p], ctypes.c_int),
+    "alll_residual": ([_vp, ctypes.POINTER(ResidualResult), _u64p, _u32p, _u32p, _u64p, _u32p], ctypes.c_int),
+    "alll_group_residual": ([_vp, ctypes.POINTER(ResidualResult), _u64p, _u32p, _u32p, _u64p, _u32p], ctypes.c_int),
 }
 
 _lib = None

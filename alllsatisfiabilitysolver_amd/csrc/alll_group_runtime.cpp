@@ -16,6 +16,7 @@
 #include "alll_group_dev.h"
 #include "alll_propagate.h"
 #include "alll_rt_util.h"
+#include "alll_residual.h"
 #include "alll_score.h"
 
 using namespace alll;
@@ -290,6 +291,33 @@ int alll_group_set_var_thresholds(alll_group* g, uint64_t item, const uint32_t* 
     return ALLL_OK;
 }
 
+// What the propagation, the scores and the residual hand to their drivers: the union's clauses and
+// sizes and the group's tables (thr == nullptr: no item has thresholds).  The item of every word is
+// built and uploaded at the first call.
+static int group_prop_args(alll_group* g, const CtxAccess& a, PropArgs* p) {
+    const uint32_t n = g->d.n_items;
+    if (!g->d_word_item) {
+        std::vector<uint32_t> word_item(a.b->n_words, 0u);
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t w = 0; w < g->items[i].n_words; ++w) word_item[g->items[i].word_base + w] = i;
+        if (int rc = upload(g, &g->d_word_item, word_item.data(), word_item.size())) return rc;
+    }
+    *p = PropArgs{};
+    p->lits = a.cv->lits;
+    p->offs = a.cv->offs;
+    p->m = a.cv->m;
+    p->k = a.cv->k;
+    p->n_vars = a.b->n_vars;
+    p->n_words = a.b->n_words;
+    p->n_items = n;
+    p->thr = const_cast<uint32_t*>(g->d_thr);
+    p->words = g->d.words;
+    p->wbias = g->d_wbias;
+    p->word_item = g->d_word_item;
+    p->clause_base = g->d.clause_base;
+    return ALLL_OK;
+}
+
 // Unit propagation of every item's pins at once: the context's three kernels over the
 // union, the items' records apart; a global round is every unfinished item's own round.
 int alll_group_propagate_pins(alll_group* g, uint64_t max_rounds, alll_propagate_result* results) {
@@ -305,25 +333,8 @@ int alll_group_propagate_pins(alll_group* g, uint64_t max_rounds, alll_propagate
     const uint32_t n = g->d.n_items;
     std::vector<uint8_t> on(n, 0);
     if (g->d_thr) on = g->biased;
-    if (g->d_thr && !g->d_word_item) {
-        std::vector<uint32_t> word_item(a.b->n_words, 0u);
-        for (uint32_t i = 0; i < n; ++i)
-            for (uint32_t w = 0; w < g->items[i].n_words; ++w) word_item[g->items[i].word_base + w] = i;
-        if ((rc = upload(g, &g->d_word_item, word_item.data(), word_item.size()))) return rc;
-    }
     PropArgs p{};
-    p.lits = a.cv->lits;
-    p.offs = a.cv->offs;
-    p.m = a.cv->m;
-    p.k = a.cv->k;
-    p.n_vars = a.b->n_vars;
-    p.n_words = a.b->n_words;
-    p.n_items = n;
-    p.thr = const_cast<uint32_t*>(g->d_thr);
-    p.words = g->d.words;
-    p.wbias = g->d_wbias;
-    p.word_item = g->d_word_item;
-    p.clause_base = g->d.clause_base;
+    if ((rc = group_prop_args(g, a, &p))) return rc;
     if ((rc = prop_drive(p, on.data(), max_rounds, results, g->stream))) return rc;
     for (uint32_t i = 0; i < n; ++i) {
         const GroupItem& it = g->items[i];
@@ -353,25 +364,8 @@ int alll_group_var_scores(alll_group* g, alll_split_result* results, uint64_t* s
                     (unsigned long long)n_scores, (unsigned long long)want);
     HIP_TRY(hipSetDevice(g->device));
     const CtxAccess a = ctx_access(g->ctx);
-    if (!g->d_word_item) {
-        std::vector<uint32_t> word_item(a.b->n_words, 0u);
-        for (uint32_t i = 0; i < n; ++i)
-            for (uint32_t w = 0; w < g->items[i].n_words; ++w) word_item[g->items[i].word_base + w] = i;
-        if ((rc = upload(g, &g->d_word_item, word_item.data(), word_item.size()))) return rc;
-    }
     PropArgs p{};
-    p.lits = a.cv->lits;
-    p.offs = a.cv->offs;
-    p.m = a.cv->m;
-    p.k = a.cv->k;
-    p.n_vars = a.b->n_vars;
-    p.n_words = a.b->n_words;
-    p.n_items = n;
-    p.thr = const_cast<uint32_t*>(g->d_thr);  // (nullptr: no item has thresholds)
-    p.words = g->d.words;
-    p.wbias = g->d_wbias;
-    p.word_item = g->d_word_item;
-    p.clause_base = g->d.clause_base;
+    if ((rc = group_prop_args(g, a, &p))) return rc;
     std::vector<uint32_t> item_vars(2ull * n);
     for (uint32_t i = 0; i < n; ++i) {
         item_vars[2 * i] = g->items[i].var_base;
@@ -385,6 +379,34 @@ int alll_group_var_scores(alll_group* g, alll_split_result* results, uint64_t* s
             scores += 2ull * it.n_vars;
         }
     return ALLL_OK;
+}
+
+// The residual formula of every item at once: one pass of the context's compaction
+// kernels over the union; they write the items' arrays one after another, in local numbering.
+int alll_group_residual(alll_group* g, alll_residual_result* results, uint64_t* offsets, uint32_t* literals,
+                        uint32_t* var_map, uint64_t* clause_map, uint32_t* thr_out) {
+    if (!g || !results) return fail(ALLL_ERR_INVALID_ARG, "residual: null argument");
+    int rc;
+    if ((rc = ctx_bias_supported(g->ctx))) return rc;
+    const uint32_t n = g->d.n_items;
+    HIP_TRY(hipSetDevice(g->device));
+    const CtxAccess a = ctx_access(g->ctx);
+    PropArgs p{};
+    if ((rc = group_prop_args(g, a, &p))) return rc;
+    std::vector<ResidItem> items(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const GroupItem& it = g->items[i];
+        items[i] = ResidItem{it.var_base, it.n_vars, it.word_base, it.n_words, it.clause_base, it.n_clauses};
+    }
+    // the union's literal count: the capacity of the literal array
+    uint64_t n_lits = p.m * p.k;
+    if (!p.k && p.m) {
+        uint32_t last = 0;
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        HIP_TRY(hipMemcpy(&last, p.offs + p.m, 4, hipMemcpyDeviceToHost));
+        n_lits = last;
+    }
+    return resid_drive(p, items, n_lits, results, ResidOut{offsets, literals, var_map, clause_map, thr_out}, g->stream);
 }
 
 int alll_group_get_var_thresholds(alll_group* g, uint64_t item, uint32_t* out, uint64_t n) {

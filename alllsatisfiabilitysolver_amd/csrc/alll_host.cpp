@@ -646,6 +646,66 @@ int alll_pinned_scores(const alll_problem* prob, const uint32_t* thr, uint64_t n
     return ALLL_OK;
 }
 
+// The residual formula (include/alll.h): a pass that classifies every clause and marks the variables
+// of the free occurrences in kept clauses, the renumbering of the marked variables, and a second pass
+// that writes the kept clauses' free occurrences.
+int alll_pinned_residual(const alll_problem* prob, const uint32_t* thr, uint64_t n, alll_residual_result* res,
+                         uint64_t* offsets, uint32_t* literals, uint32_t* var_map, uint64_t* clause_map,
+                         uint32_t* thr_out) {
+    if (int rc = pinned_validate(prob, thr, n, res, "pinned residual", true)) return rc;
+    const uint64_t m = prob->n_clauses;
+    const uint32_t nv = prob->n_vars;
+    auto is_free = [&](uint32_t l) { return !thr || (thr[l >> 1] != 0u && thr[l >> 1] != 0xFFFFFFFFu); };
+    auto dropped = [&](uint64_t c) {  // a true literal
+        for (uint64_t j = prob->offsets[c]; j < prob->offsets[c + 1]; ++j) {
+            const uint32_t l = prob->literals[j];
+            if (!is_free(l) && thr[l >> 1] == ((l & 1u) ? 0u : 0xFFFFFFFFu)) return true;
+        }
+        return false;
+    };
+    alll_residual_result r{0, 0, 0, m, 0, 0};
+    std::vector<uint8_t> keep(m, 0);
+    std::vector<uint32_t> new_of(nv, 0);  // 1: kept; then the residual index
+    for (uint64_t c = 0; c < m; ++c) {
+        if (dropped(c)) continue;
+        keep[c] = 1;
+        uint64_t f = 0;
+        for (uint64_t j = prob->offsets[c]; j < prob->offsets[c + 1]; ++j)
+            if (is_free(prob->literals[j])) {
+                new_of[prob->literals[j] >> 1] = 1;
+                ++f;
+            }
+        r.n_clauses += 1;
+        r.n_literals += f;
+        if (!f) {
+            if (!r.n_falsified) r.first_falsified = c;
+            r.n_falsified += 1;
+        }
+    }
+    for (uint32_t v = 0; v < nv; ++v)
+        if (new_of[v]) {
+            if (var_map) var_map[r.n_vars] = v;
+            if (thr_out) thr_out[r.n_vars] = thr ? thr[v] : 0x80000000u;
+            new_of[v] = r.n_vars++;
+        }
+    uint64_t jc = 0, jl = 0;
+    for (uint64_t c = 0; c < m && (offsets || literals || clause_map); ++c) {
+        if (!keep[c]) continue;
+        if (offsets) offsets[jc] = jl;
+        if (clause_map) clause_map[jc] = c;
+        ++jc;
+        for (uint64_t j = prob->offsets[c]; j < prob->offsets[c + 1]; ++j) {
+            const uint32_t l = prob->literals[j];
+            if (!is_free(l)) continue;
+            if (literals) literals[jl] = 2u * new_of[l >> 1] + (l & 1u);
+            ++jl;
+        }
+    }
+    if (offsets) offsets[r.n_clauses] = r.n_literals;
+    *res = r;
+    return ALLL_OK;
+}
+
 int alll_dimacs_parse(const char* buf, uint64_t len, uint32_t* n_vars, uint64_t* n_clauses,
                       uint64_t* offsets, uint32_t* literals, uint64_t* n_literals) {
     if (!buf && len) return ALLL_ERR_INVALID_ARG;

@@ -25,6 +25,7 @@
 #include "alll_layout.h"
 #include "alll_propagate.h"
 #include "alll_rt_util.h"
+#include "alll_residual.h"
 #include "alll_score.h"
 
 using namespace alll;
@@ -1460,6 +1461,29 @@ int alll_var_scores(alll_ctx* c, uint64_t* scores, uint64_t n_scores, alll_split
     if ((rc = score_drive(a, {0u, c->n_vars}, res, scores ? &S : nullptr, c->stream))) return rc;
     if (scores && c->n_vars) memcpy(scores, S.data(), 16ull * c->n_vars);
     return ALLL_OK;
+}
+
+// The residual formula under the context's thresholds: a pass of its own kernels
+// and scratch on the drained stream; nothing of the context is written.
+int alll_residual(alll_ctx* c, alll_residual_result* res, uint64_t* offsets, uint32_t* literals, uint32_t* var_map,
+                  uint64_t* clause_map, uint32_t* thr_out) {
+    if (!c || !res) return fail(ALLL_ERR_INVALID_ARG, "residual: null argument");
+    if (c->grp) return fail(ALLL_ERR_INVALID_ARG, "residual: the context belongs to a group (alll_group_residual)");
+    int rc;
+    if ((rc = bias_supported(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const LoopBuffers& b = c->b;
+    PropArgs a{};
+    a.lits = c->cv.lits;
+    a.offs = c->cv.offs;
+    a.m = c->cv.m;
+    a.k = c->cv.k;
+    a.n_vars = b.n_vars;
+    a.n_words = b.n_words;
+    a.n_items = 1;
+    a.thr = (b.thr && c->d_thr) ? c->d_thr : nullptr;
+    const std::vector<ResidItem> items{ResidItem{0u, c->n_vars, 0u, b.n_words, 0u, (uint32_t)c->cv.m}};
+    return resid_drive(a, items, c->n_lits, res, ResidOut{offsets, literals, var_map, clause_map, thr_out}, c->stream);
 }
 
 int alll_track_best(alll_ctx* c, int on) {

@@ -166,6 +166,81 @@ def var_scores(n_vars: int, offsets, literals, thr=None):
     return scores, res.as_dict()
 
 
+class _ResidualArrays:
+    """The output arrays of a residual call at their capacities (sums of the items' original sizes),
+    and their cut into one dict per item."""
+
+    def __init__(self, sizes, with_arrays: bool):
+        # sizes: per item (n_vars, n_clauses, n_literals)
+        self.on = with_arrays
+        if not with_arrays:  # (the counts alone: nothing to hold)
+            return
+        nv, m, nl = (sum(s[k] for s in sizes) for k in range(3))
+        self.offsets = np.zeros(m + len(sizes), np.uint64)
+        self.literals = np.zeros(max(1, nl), np.uint32)
+        self.var_map = np.zeros(max(1, nv), np.uint32)
+        self.clause_map = np.zeros(max(1, m), np.uint64)
+        self.thr = np.zeros(max(1, nv), np.uint32)
+
+    def args(self):
+        if not self.on:
+            return (None,) * 5
+        return (_p(self.offsets, _u64p), _p(self.literals, _u32p), _p(self.var_map, _u32p), _p(self.clause_map, _u64p),
+                _p(self.thr, _u32p))
+
+    def items(self, records) -> List[dict]:
+        out, c0, l0, v0 = [], 0, 0, 0
+        for i, r in enumerate(records):
+            d = {"n_vars": r["n_vars"], "n_clauses": r["n_clauses"], "n_literals": r["n_literals"],
+                 "n_falsified": r["n_falsified"], "first_falsified": r["first_falsified"]}
+            if self.on:
+                c1, l1, v1 = c0 + r["n_clauses"], l0 + r["n_literals"], v0 + r["n_vars"]
+                d.update(offsets=self.offsets[c0 + i:c1 + i + 1].copy(), literals=self.literals[l0:l1].copy(),
+                         var_map=self.var_map[v0:v1].copy(), clause_map=self.clause_map[c0:c1].copy(),
+                         thr=self.thr[v0:v1].copy())
+                c0, l0, v0 = c1, l1, v1
+            out.append(d)
+        return out
+
+
+def residual_instance(n_vars: int, offsets, literals, thr=None) -> dict:
+    """alll_pinned_residual: the residual formula under thresholds thr (host-only; None: every
+    variable free): the clauses without a true literal, reduced to their free literals, over the
+    variables that still occur, renumbered in ascending order (include/alll.h).  Returns {"n_vars",
+    "n_clauses", "n_literals", "offsets", "literals", "var_map", "clause_map", "thr", "n_falsified",
+    "first_falsified"}: (n_vars, offsets, literals) is the residual problem, thr its thresholds,
+    var_map / clause_map the original variable / clause of every residual one."""
+    offs = np.ascontiguousarray(offsets, np.uint64)
+    lits = np.ascontiguousarray(literals, np.uint32)
+    m = max(0, offs.size - 1)
+    prob = N.Problem(int(n_vars), 0, m, _p(offs, _u64p), _p(lits, _u32p))
+    if thr is None:
+        t, n = None, 0
+    else:
+        thr = np.ascontiguousarray(thr, np.uint32)
+        t, n = _p(thr, _u32p), thr.size
+    # (the capacities: the literal count is offsets[m] once the call has validated the instance)
+    out = _ResidualArrays([(int(n_vars), m, lits.size)], True)
+    res = N.ResidualResult()
+    N.check(N.lib().alll_pinned_residual(ctypes.byref(prob), t, n, ctypes.byref(res), *out.args()), "pinned_residual")
+    return out.items([res.as_dict()])[0]
+
+
+def lift_assignment(n_vars: int, thr, var_map, words_res) -> np.ndarray:
+    """The full assignment of a residual one (bit-packed, ceil(n_vars / 32) words): the pinned
+    variables of thr (None: none) at their pins, the kept variables var_map[u] at bit u of words_res,
+    every other variable 0."""
+    bits = np.zeros(32 * ((int(n_vars) + 31) // 32), np.uint8)
+    if thr is not None:
+        bits[:n_vars][np.asarray(thr, np.uint32) == 0xFFFFFFFF] = 1
+    var_map = np.asarray(var_map, np.int64)
+    res = np.unpackbits(np.ascontiguousarray(words_res, np.uint32).view(np.uint8), bitorder="little")
+    if res.size < var_map.size:
+        raise ValueError(f"{res.size} residual bits for {var_map.size} kept variables")
+    bits[var_map] = res[:var_map.size]
+    return np.packbits(bits, bitorder="little").view(np.uint32)
+
+
 # ----------------------------------------------------------------------------- Solver
 class Solver:
     """Owns one device solver context (alll_ctx).  probabilities: P(x_v = 1) per variable (0 and 1
@@ -268,6 +343,15 @@ class Solver:
         scores = np.zeros(2 * self.n_vars, np.uint64)
         N.check(self._L.alll_var_scores(self._ctx, _p(scores, _u64p), scores.size, ctypes.byref(res)), "alll_var_scores")
         return scores, res.as_dict()
+
+    def residual(self, with_arrays: bool = True) -> dict:
+        """alll_residual: the residual formula under the solver's current thresholds (none: every
+        variable free), compacted on the device.  At any time; nothing of the solver changes.  Returns
+        the dict of residual_instance, the host form; with_arrays=False: the counts alone."""
+        out = _ResidualArrays([(self.n_vars, self.m, self.literals.size)], with_arrays)
+        res = N.ResidualResult()
+        N.check(self._L.alll_residual(self._ctx, ctypes.byref(res), *out.args()), "alll_residual")
+        return out.items([res.as_dict()])[0]
 
     def set_host_exchange(self, exchange):
         """exchange(op, buf: numpy uint8 view, bytes_per_rank_or_total) -> None; see
@@ -475,6 +559,7 @@ class _ItemSolver:
         keep = {}  # one converted copy per distinct pair of arrays: shared problems stay shared
         arr = (N.Problem * max(1, self.n_items))()
         self.n_vars = []
+        self._sizes = []  # per item (n_vars, n_clauses, n_literals)
         for i, (n_vars, offsets, literals) in enumerate(problems):
             key = (id(offsets), id(literals))
             if key not in keep:
@@ -483,6 +568,7 @@ class _ItemSolver:
             _, _, offs, lits = keep[key]
             arr[i] = N.Problem(int(n_vars), 0, max(0, offs.size - 1), _p(offs, _u64p), _p(lits, _u32p))
             self.n_vars.append(int(n_vars))
+            self._sizes.append((int(n_vars), max(0, offs.size - 1), int(offs[-1]) if offs.size else 0))
         opt = N.Options()
         self._L.alll_default_options(ctypes.byref(opt))
         opt.max_iters, opt.device = max_iters, device
@@ -645,6 +731,15 @@ class GroupSolver(_ItemSolver):
         cuts = np.cumsum([2 * n for n in self.n_vars])[:-1]
         return [res[i].as_dict() for i in range(self.n_items)], np.split(scores, cuts)
 
+    def residuals(self, with_arrays: bool = True) -> List[dict]:
+        """alll_group_residual: Solver.residual for every item in one pass over the union.  Returns one
+        dict per item, in the item's own clause and variable numbering; an item without thresholds has
+        every variable free.  with_arrays=False: the counts alone."""
+        out = _ResidualArrays(self._sizes, with_arrays)
+        res = (N.ResidualResult * max(1, self.n_items))()
+        N.check(self._L.alll_group_residual(self._h, res, *out.args()), "alll_group_residual")
+        return out.items([res[i].as_dict() for i in range(self.n_items)])
+
     def epoch_counters(self) -> dict:
         """Solver.epoch_counters of the union."""
         out = np.zeros(4, np.uint64)
@@ -741,6 +836,50 @@ def solve_cubes_propagated(n_vars: int, offsets, literals, cubes, seeds=None, ma
     as well, and the others run, in a second solver of the same kind, under their propagated
     thresholds.  The return value is solve_cubes', the indices are the caller's."""
     return _solve_cubes(n_vars, offsets, literals, cubes, seeds, max_iters, True)
+
+
+def solve_cubes_residual(n_vars: int, offsets, literals, cubes, seeds=None, max_iters: int = 0):
+    """solve_cubes_propagated on the residual formulas: after the depth-0 filter and the propagation
+    (a GroupSolver of the live cubes), every surviving cube's instance is reduced under its propagated
+    thresholds on the device (GroupSolver.residuals) and the residual problems run, under their
+    carried thresholds and the cubes' seeds, in a BatchSolver when every one of them fits a batch item
+    (batch_fits), else in a GroupSolver -- the choice is made on the residuals' sizes, not on the
+    instance's.  The winner is solve_cubes': the solved cube with the fewest iterations, the lowest
+    index on a tie; its words are lifted (lift_assignment).  Returns (cube index, stats, the full
+    assignment_words), or (None, None, None) when no cube is left or max_iters capped every one.  A
+    residual's trajectory is not the pinned instance's (other variable indices, other Philox
+    streams): the iteration counts differ from solve_cubes_propagated's."""
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    literals = np.ascontiguousarray(literals, np.uint32)
+    cubes = list(cubes)
+    seeds = list(range(1, len(cubes) + 1)) if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != len(cubes):
+        raise ValueError(f"{len(cubes)} cubes, {len(seeds)} seeds")
+    thrs = [cube_thresholds(n_vars, c) for c in cubes]
+    live = [i for i, t in enumerate(thrs) if pinned_conflict(n_vars, offsets, literals, t) is None]
+    if not live:
+        return None, None, None
+    with GroupSolver([(n_vars, offsets, literals)] * len(live), [seeds[i] for i in live]) as g:
+        for k, i in enumerate(live):
+            g.set_thresholds(k, thrs[i])
+        keep = [k for k, r in enumerate(g.propagate_pins()) if r["status"] != N.PROP_CONFLICT]
+        if not keep:
+            return None, None, None
+        res = g.residuals()
+        full = {k: g.thresholds(k) for k in keep}
+    fits = all(batch_fits(res[k]["n_vars"], res[k]["n_clauses"], res[k]["n_literals"]) for k in keep)
+    cls = BatchSolver if fits else GroupSolver
+    with cls([(res[k]["n_vars"], res[k]["offsets"], res[k]["literals"]) for k in keep], [seeds[live[k]] for k in keep],
+             max_iters=max_iters) as b:
+        for j, k in enumerate(keep):
+            b.set_thresholds(j, res[k]["thr"])
+        st = b.solve(first_solved=True)
+        solved = [j for j, r in enumerate(st) if r["solved"]]
+        if not solved:
+            return None, None, None
+        best = min(solved, key=lambda j: (st[j]["n_iterations"], j))
+        k = keep[best]
+        return live[k], st[best], lift_assignment(n_vars, full[k], res[k]["var_map"], b.assignment_words(best))
 
 
 def split_cubes(n_vars: int, offsets, literals, depth: int, base=(), device: int = -1):

@@ -330,6 +330,47 @@ typedef struct alll_split_result {
  * wrong n_scores: ALLL_ERR_INVALID_ARG.  (No reference counterpart.) */
 int alll_var_scores(alll_ctx* ctx, uint64_t* scores, uint64_t n_scores, alll_split_result* res);
 
+/* The residual formula under the pins: what is left of the instance once the
+ * pinned variables are decided.  The literal states under thresholds thr are those of the propagation
+ * above (true, false, free; a bias that is not a pin is free); without thresholds every variable is
+ * free.
+ *  - A clause with a true literal is dropped.
+ *  - Every other clause is kept; its residual clause is its free literal occurrences, in their order,
+ *    with multiplicity (x x !y with y pinned 1 becomes x x; x !x stays x !x).
+ *  - A kept clause with no free occurrence (falsified, or empty in the original) is kept as an empty
+ *    clause and counted in n_falsified; first_falsified is the smallest such original index, the
+ *    original n_clauses when there is none.
+ *  - Kept clauses keep their relative order: clause_map[j] is the original index of residual clause j,
+ *    and it ascends.
+ *  - A variable is kept when it has a free occurrence in a kept clause.  Kept variables are renumbered
+ *    in ascending order: var_map[u] is the original variable of residual variable u, and a residual
+ *    literal is 2 u + sign.
+ *  - thr_out[u] = thr[var_map[u]]: biases are carried; without thresholds it is 0x80000000.
+ *  - offsets are 64-bit, start at 0 and have n_clauses + 1 entries, as in alll_problem.
+ * Integers and a stable order: the result does not depend on any execution order.  No subsumption,
+ * pure-literal or duplicate removal: the residual is the formula as written, minus what the pins
+ * decide.
+ * Lift: the full assignment of a residual assignment has the pinned variables at their pins, the kept
+ * variables at their residual bits and every other variable 0.  With n_falsified == 0, an assignment
+ * that satisfies the residual lifts to one that satisfies the original. */
+typedef struct alll_residual_result {
+    uint64_t n_clauses;           /* kept clauses */
+    uint64_t n_literals;          /* their free literal occurrences */
+    uint64_t n_falsified;         /* kept clauses without a free occurrence */
+    uint64_t first_falsified;     /* the smallest of them (original index); the original n_clauses: none */
+    uint32_t n_vars;              /* kept variables */
+    uint32_t pad;                 /* 0 */
+} alll_residual_result;           /* 40 bytes */
+/* The residual of the context's instance under its current thresholds, compacted on the device.
+ * Every output array may be NULL (the record alone); the capacities are the original sizes -- offsets
+ * n_clauses + 1, literals the original literal count, var_map and thr_out n_vars, clause_map
+ * n_clauses -- which the residual never exceeds; only the used prefixes are written.  Allowed at any
+ * time: the call drains the stream and changes nothing in the context.  It refuses the contexts
+ * alll_set_var_thresholds refuses, with ALLL_ERR_UNSUPPORTED, before any device work; a null context,
+ * a null res or a context that belongs to a group: ALLL_ERR_INVALID_ARG.  (No reference counterpart.) */
+int alll_residual(alll_ctx* ctx, alll_residual_result* res, uint64_t* offsets, uint32_t* literals, uint32_t* var_map,
+                  uint64_t* clause_map, uint32_t* thr_out);
+
 /* Introspection of the last iteration (parity tests): violated bitmask of the last eval
  * pass (ceil(n_clauses/64) words) and the MIS picked from it (ascending clause order). */
 int alll_get_violated_mask(alll_ctx* ctx, uint64_t* out, uint64_t n_words);
@@ -526,6 +567,15 @@ int alll_group_get_var_thresholds(alll_group* g, uint64_t item, uint32_t* out, u
  * ended does not matter (the scores are a function of clauses and thresholds only).  At any time;
  * nothing in the group changes. */
 int alll_group_var_scores(alll_group* g, alll_split_result* results, uint64_t* scores, uint64_t n_scores);
+/* alll_residual over the union, every item in one pass (results: n_items entries): item i's record
+ * and arrays are exactly those of a context of its own, in its local clause and variable numbering.
+ * Every array may be NULL; the arrays are laid densely, one item after another in item order: item
+ * i's offsets has results[i].n_clauses + 1 entries and starts at 0, its literals results[i].n_literals
+ * entries, and so on (capacities: the sums of the items' original sizes, offsets n_clauses_i + 1
+ * each).  An item without thresholds has every variable free.  At any time; nothing in the group
+ * changes. */
+int alll_group_residual(alll_group* g, alll_residual_result* results, uint64_t* offsets, uint32_t* literals,
+                        uint32_t* var_map, uint64_t* clause_map, uint32_t* thr_out);
 /* alll_track_best / alll_get_best per item (the contract above): switched for every
  * item at once, before the group's first iteration; the same ALLL_ERR_UNSUPPORTED contexts.  Every
  * item keeps its own record, in its local variable numbering and its own pass count, exactly that
@@ -617,6 +667,16 @@ int alll_pinned_propagate(const alll_problem* prob, uint32_t* thr, uint64_t n, u
  * the null thr); nothing is written on an error. */
 int alll_pinned_scores(const alll_problem* prob, const uint32_t* thr, uint64_t n, uint64_t* scores,
                        alll_split_result* res);
+
+/* The residual of alll_residual on the host (the semantics above) under thresholds thr (n == n_vars
+ * entries; thr == NULL: every variable free, n is not looked at).  Every output array may be NULL;
+ * the capacities are the original sizes: offsets n_clauses + 1, literals the original literal count,
+ * var_map and thr_out n_vars, clause_map n_clauses.  Validation and error codes are those of
+ * alll_pinned_scores; nothing is written on an error.  (The batch form: batch items are small, and
+ * this function serves them.) */
+int alll_pinned_residual(const alll_problem* prob, const uint32_t* thr, uint64_t n, alll_residual_result* res,
+                         uint64_t* offsets, uint32_t* literals, uint32_t* var_map, uint64_t* clause_map,
+                         uint32_t* thr_out);
 
 /* The reference's own initial assignment (VariablesArray.h:23-34) in the reference-RNG mode
  * (ALLL_FLAG_REFERENCE_RNG): `rd_state` is the random_device stand-in's state
