@@ -12,12 +12,13 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
             -Iinclude -I$(SRC) -I$(ROCM)/include $(EXTRA)
 LIB := $(PKG)/liballl.so
 OBJS := $(SRC)/alll_kernels.o $(SRC)/alll_stream.o $(SRC)/alll_refrng.o $(SRC)/alll_runtime.o $(SRC)/alll_layout.o $(SRC)/alll_host.o \
-        $(SRC)/alll_small.o $(SRC)/alll_batch.o $(SRC)/alll_batch_runtime.o $(SRC)/alll_propagate.o $(SRC)/alll_score.o $(SRC)/alll_residual.o \
+        $(SRC)/alll_small.o $(SRC)/alll_batch.o $(SRC)/alll_batch_runtime.o $(SRC)/alll_propagate.o $(SRC)/alll_score.o $(SRC)/alll_probe.o $(SRC)/alll_residual.o \
         $(SRC)/alll_group.o $(SRC)/alll_group_runtime.o
 GROUP_H := $(SRC)/alll_group.h $(SRC)/alll_group_dev.h
 PROP_H := $(SRC)/alll_propagate.h
 SCORE_H := $(SRC)/alll_score.h
 RESID_H := $(SRC)/alll_residual.h
+PROBE_H := $(SRC)/alll_probe.h
 
 all: $(LIB)
 
@@ -30,7 +31,7 @@ $(SRC)/alll_stream.o: $(SRC)/alll_stream.hip $(SRC)/alll_internal.h
 $(SRC)/alll_refrng.o: $(SRC)/alll_refrng.hip $(SRC)/alll_internal.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(SRC)/alll_runtime.o: $(SRC)/alll_runtime.cpp $(SRC)/alll_layout.h $(SRC)/alll_internal.h $(SRC)/alll_rt_util.h $(GROUP_H) $(PROP_H) $(SCORE_H) $(RESID_H) include/alll.h
+$(SRC)/alll_runtime.o: $(SRC)/alll_runtime.cpp $(SRC)/alll_layout.h $(SRC)/alll_internal.h $(SRC)/alll_rt_util.h $(GROUP_H) $(PROP_H) $(SCORE_H) $(RESID_H) $(PROBE_H) include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 $(SRC)/alll_layout.o: $(SRC)/alll_layout.cpp $(SRC)/alll_layout.h $(SRC)/alll_internal.h include/alll.h
@@ -45,6 +46,10 @@ $(SRC)/alll_propagate.o: $(SRC)/alll_propagate.hip $(PROP_H) $(SRC)/alll_group.h
 
 # split scores of the free variables: the scoring kernels and their host driver
 $(SRC)/alll_score.o: $(SRC)/alll_score.hip $(SCORE_H) $(PROP_H) $(SRC)/alll_group.h $(SRC)/alll_internal.h $(SRC)/alll_rt_util.h include/alll.h
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
+# failed-literal probing: 64 propagations per clause pass, the kernels and their host driver
+$(SRC)/alll_probe.o: $(SRC)/alll_probe.hip $(PROBE_H) $(PROP_H) $(SRC)/alll_group.h $(SRC)/alll_internal.h $(SRC)/alll_rt_util.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 # the residual formula under the pins: the compaction kernels and their host driver

@@ -552,13 +552,11 @@ int alll_pinned_conflict(const alll_problem* prob, const uint32_t* thr, uint64_t
 
 // Unit propagation of the pins (include/alll.h): rounds over all clauses, every clause judged against
 // the thresholds of the round's start, the forced literals applied at once.
-int alll_pinned_propagate(const alll_problem* prob, uint32_t* thr, uint64_t n, uint64_t max_rounds,
-                          alll_propagate_result* res) {
-    if (int rc = pinned_validate(prob, thr, n, res, "pinned propagate")) return rc;
+// (the helper alll_pinned_propagate and alll_pinned_probe share: a validated instance, thr in place;
+// force: n_vars zeros on entry and at the return -- bit 0: forced to 1, bit 1: forced to 0)
+static alll_propagate_result propagate_rounds(const alll_problem* prob, uint32_t* thr, uint64_t max_rounds,
+                                              std::vector<uint8_t>& force, std::vector<uint32_t>& touched) {
     const uint64_t m = prob->n_clauses;
-    const uint32_t nv = prob->n_vars;
-    std::vector<uint8_t> force(nv, 0);  // bit 0: forced to 1, bit 1: forced to 0
-    std::vector<uint32_t> touched;
     alll_propagate_result r{m, 0, 0, ALLL_PROP_FIXPOINT};
     for (;;) {
         uint64_t conflict = m;
@@ -590,6 +588,7 @@ int alll_pinned_propagate(const alll_problem* prob, uint32_t* thr, uint64_t n, u
         }
         if (touched.empty()) break;  // (fixpoint)
         if (max_rounds && r.rounds >= max_rounds) {
+            for (uint32_t v : touched) force[v] = 0;
             r.status = ALLL_PROP_ROUND_CAP;
             break;
         }
@@ -600,7 +599,57 @@ int alll_pinned_propagate(const alll_problem* prob, uint32_t* thr, uint64_t n, u
         r.n_forced += touched.size();
         r.rounds += 1;
     }
-    *res = r;
+    return r;
+}
+
+int alll_pinned_propagate(const alll_problem* prob, uint32_t* thr, uint64_t n, uint64_t max_rounds,
+                          alll_propagate_result* res) {
+    if (int rc = pinned_validate(prob, thr, n, res, "pinned propagate")) return rc;
+    std::vector<uint8_t> force(prob->n_vars, 0);
+    std::vector<uint32_t> touched;
+    *res = propagate_rounds(prob, thr, max_rounds, force, touched);
+    return ALLL_OK;
+}
+
+// Failed-literal probing (include/alll.h): every probe is the propagation above on a copy of the
+// thresholds with the probe's literal pinned true.
+int alll_pinned_probe(const alll_problem* prob, const uint32_t* thr, uint64_t n, const uint32_t* probes, uint64_t n_probes,
+                      uint64_t max_rounds, alll_propagate_result* results, uint32_t* pm_rows, uint32_t* pv_rows) {
+    if (int rc = pinned_validate(prob, thr, n, results, "pinned probe", true)) return rc;
+    if (n_probes && !probes) {
+        g_host_err = "pinned probe: null probes";
+        return ALLL_ERR_INVALID_ARG;
+    }
+    const uint32_t nv = prob->n_vars;
+    for (uint64_t p = 0; p < n_probes; ++p)
+        if (probes[p] >= 2ull * nv) {
+            g_host_err = "pinned probe: probe " + std::to_string(p) + " is literal " + std::to_string(probes[p]) + " of " +
+                         std::to_string(nv) + " variables";
+            return ALLL_ERR_INVALID_ARG;
+        }
+    const size_t nw = ((size_t)nv + 31) / 32;
+    std::vector<uint32_t> base(nv, 0x80000000u), t;  // (no thresholds: every variable a fair coin)
+    if (thr && nv) memcpy(base.data(), thr, 4 * (size_t)nv);
+    std::vector<uint8_t> force(nv, 0);
+    std::vector<uint32_t> touched;
+    for (uint64_t p = 0; p < n_probes; ++p) {
+        const uint32_t l = probes[p], v = l >> 1;
+        alll_propagate_result r{prob->n_clauses, 0, 0, ALLL_PROP_NONE};
+        t = base;
+        if (base[v] != 0u && base[v] != 0xFFFFFFFFu) {
+            t[v] = (l & 1u) ? 0u : 0xFFFFFFFFu;
+            r = propagate_rounds(prob, t.data(), max_rounds, force, touched);
+        }
+        results[p] = r;
+        for (int which = 0; which < 2; ++which) {
+            uint32_t* row = which ? pv_rows : pm_rows;
+            if (!row) continue;
+            row += p * nw;
+            std::fill(row, row + nw, 0u);
+            for (uint32_t u = 0; u < nv; ++u)
+                if (t[u] == 0xFFFFFFFFu || (!which && t[u] == 0u)) row[u >> 5] |= 1u << (u & 31u);
+        }
+    }
     return ALLL_OK;
 }
 

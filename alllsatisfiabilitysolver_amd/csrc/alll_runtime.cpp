@@ -23,6 +23,7 @@
 #include "alll_group_dev.h"
 #include "alll_internal.h"
 #include "alll_layout.h"
+#include "alll_probe.h"
 #include "alll_propagate.h"
 #include "alll_rt_util.h"
 #include "alll_residual.h"
@@ -1461,6 +1462,36 @@ int alll_var_scores(alll_ctx* c, uint64_t* scores, uint64_t n_scores, alll_split
     if ((rc = score_drive(a, {0u, c->n_vars}, res, scores ? &S : nullptr, c->stream))) return rc;
     if (scores && c->n_vars) memcpy(scores, S.data(), 16ull * c->n_vars);
     return ALLL_OK;
+}
+
+// Failed-literal probing under the context's thresholds: rounds of its own kernels
+// and scratch on the drained stream; nothing of the context is written.
+int alll_probe_literals(alll_ctx* c, const uint32_t* probes, uint64_t n_probes, uint64_t max_rounds,
+                        alll_propagate_result* results, uint32_t* pm_rows, uint32_t* pv_rows, uint64_t n_words) {
+    if (!c || !results || (!probes && n_probes)) return fail(ALLL_ERR_INVALID_ARG, "probe literals: null argument");
+    if (c->grp) return fail(ALLL_ERR_INVALID_ARG, "probe literals: the context belongs to a group (no group form)");
+    int rc;
+    if ((rc = bias_supported(c))) return rc;
+    const LoopBuffers& b = c->b;
+    if ((pm_rows || pv_rows) && n_words != b.n_words)
+        return fail(ALLL_ERR_INVALID_ARG, "probe literals: rows of %llu words for the %u of the assignment",
+                    (unsigned long long)n_words, b.n_words);
+    for (uint64_t p = 0; p < n_probes; ++p)
+        if (probes[p] >= 2ull * c->n_vars)
+            return fail(ALLL_ERR_INVALID_ARG, "probe literals: probe %llu is literal %u of %u variables",
+                        (unsigned long long)p, probes[p], c->n_vars);
+    if (n_probes == 0) return ALLL_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    PropArgs a{};
+    a.lits = c->cv.lits;
+    a.offs = c->cv.offs;
+    a.m = c->cv.m;
+    a.k = c->cv.k;
+    a.n_vars = b.n_vars;
+    a.n_words = b.n_words;
+    a.n_items = 1;
+    a.thr = (b.thr && c->d_thr) ? c->d_thr : nullptr;
+    return probe_drive(a, probes, n_probes, max_rounds, results, pm_rows, pv_rows, c->stream);
 }
 
 // The residual formula under the context's thresholds: a pass of its own kernels

@@ -166,6 +166,42 @@ def var_scores(n_vars: int, offsets, literals, thr=None):
     return scores, res.as_dict()
 
 
+def _probe_out(n_probes: int, n_vars: int, rows: bool):
+    """The result records of a probe call and, with rows, its two arrays of n_probes x n_words words."""
+    res = (N.PropagateResult * max(1, n_probes))()
+    nw = (int(n_vars) + 31) // 32
+    pm = np.zeros((n_probes, nw), np.uint32) if rows else None
+    pv = np.zeros((n_probes, nw), np.uint32) if rows else None
+    return res, nw, pm, pv
+
+
+def _probe_ret(res, n_probes: int, rows: bool, pm, pv):
+    out = [res[i].as_dict() for i in range(n_probes)]
+    return (out, pm, pv) if rows else out
+
+
+def probe_literals(n_vars: int, offsets, literals, thr, probes, max_rounds: int = 0, rows: bool = False):
+    """alll_pinned_probe: failed-literal probing (host-only; include/alll.h).  Every probe is a literal
+    l = 2v + sign; its result is what propagate_pins returns under thr (None: every variable a fair
+    coin) with l pinned true -- a probe on a variable thr already pins: PROP_NONE.  Returns the list of
+    {"status", "rounds", "n_forced", "conflict_clause"}; rows=True: (list, pm, pv), uint32[n_probes,
+    n_words] each: the pinned variables when the probe ends and their values, bit-packed."""
+    offs = np.ascontiguousarray(offsets, np.uint64)
+    lits = np.ascontiguousarray(literals, np.uint32)
+    probes = np.ascontiguousarray(probes, np.uint32).ravel()
+    m = max(0, offs.size - 1)
+    prob = N.Problem(int(n_vars), 0, m, _p(offs, _u64p), _p(lits, _u32p))
+    if thr is None:
+        t, n = None, 0
+    else:
+        thr = np.ascontiguousarray(thr, np.uint32)
+        t, n = _p(thr, _u32p), thr.size
+    res, _, pm, pv = _probe_out(probes.size, n_vars, rows)
+    N.check(N.lib().alll_pinned_probe(ctypes.byref(prob), t, n, _p(probes, _u32p), probes.size, max_rounds, res,
+                                      _p(pm, _u32p) if rows else None, _p(pv, _u32p) if rows else None), "pinned_probe")
+    return _probe_ret(res, probes.size, rows, pm, pv)
+
+
 class _ResidualArrays:
     """The output arrays of a residual call at their capacities (sums of the items' original sizes),
     and their cut into one dict per item."""
@@ -343,6 +379,17 @@ class Solver:
         scores = np.zeros(2 * self.n_vars, np.uint64)
         N.check(self._L.alll_var_scores(self._ctx, _p(scores, _u64p), scores.size, ctypes.byref(res)), "alll_var_scores")
         return scores, res.as_dict()
+
+    def probe(self, probes, max_rounds: int = 0, rows: bool = False):
+        """alll_probe_literals: failed-literal probing under the solver's current thresholds (none:
+        every variable free) on the device, 64 probes per pass over the clauses.  At any time; nothing
+        of the solver changes.  Returns what probe_literals, the host form, returns."""
+        probes = np.ascontiguousarray(probes, np.uint32).ravel()
+        res, nw, pm, pv = _probe_out(probes.size, self.n_vars, rows)
+        N.check(self._L.alll_probe_literals(self._ctx, _p(probes, _u32p), probes.size, max_rounds, res,
+                                            _p(pm, _u32p) if rows else None, _p(pv, _u32p) if rows else None, nw),
+                "alll_probe_literals")
+        return _probe_ret(res, probes.size, rows, pm, pv)
 
     def residual(self, with_arrays: bool = True) -> dict:
         """alll_residual: the residual formula under the solver's current thresholds (none: every
@@ -945,6 +992,102 @@ def solve_cubes_split(n_vars: int, offsets, literals, depth: int, base=(), seeds
         return leaves, (None, None, None)
     win, st, words = solve_cubes_propagated(n_vars, offsets, literals, [leaves[j]["cube"] for j in live], seeds, max_iters)
     return leaves, ((None, None, None) if win is None else (live[win], st, words))
+
+
+def failed_literal_reduce(n_vars: int, offsets, literals, thr=None, n_candidates: int = 64, max_passes: int = 0,
+                          device: bool = True) -> dict:
+    """Failed-literal and necessary-assignment reduction of thresholds thr (None: every variable a fair
+    coin) by look-ahead probing; device=False: the host path (propagate_pins, var_scores,
+    probe_literals), else one Solver and its propagate_pins, var_scores and probe.  A pass
+      1. propagates the pins (a conflict ends the call: status "conflict");
+      2. takes the split scores (no open clause: status "satisfied");
+      3. takes as candidates the n_candidates free variables with the largest T(v) = S[2v] + S[2v+1] > 0,
+         ties to the lowest variable;
+      4. probes both literals of each, with rows;
+      5. both in PROP_CONFLICT: status "conflict";
+      6. one in PROP_CONFLICT: its negation is pinned (a failed literal);
+      7. both in PROP_FIXPOINT: a variable that both rows pin to the same value and the base leaves free
+         is pinned (a necessary assignment);
+      8. nothing new pinned: the call ends, status "open"; else after max_passes passes (when non-zero);
+         else the next pass.
+    The pins of a pass are collected in the candidates' order, the failed literals first; a variable
+    already pinned in the pass is not pinned again.  Returns {"thr", "status", "passes", "n_failed",
+    "n_necessary", "lookahead_var", "candidates"}: candidates is the last pass's list of (var, result of
+    2 var, result of 2 var + 1), empty when that pass ended in step 1 or 2; lookahead_var the candidate,
+    among those whose two probes ended in PROP_FIXPOINT, with the largest (n_forced_pos + 1) *
+    (n_forced_neg + 1), ties to the larger T, then the lowest variable; n_vars when there is none.
+    Integers and fixed tie rules only: both paths return equal dicts."""
+    n = int(n_vars)
+    if n_candidates < 1:
+        raise ValueError("n_candidates must be at least 1")
+    thr = np.full(n, 1 << 31, np.uint32) if thr is None else np.array(thr, np.uint32)
+    if thr.size != n:
+        raise ValueError(f"{thr.size} thresholds for {n} variables")
+    solver = Solver(n, offsets, literals) if device else None
+    out = {"status": "open", "passes": 0, "n_failed": 0, "n_necessary": 0, "lookahead_var": n, "candidates": []}
+    try:
+        while True:
+            out["passes"] += 1
+            out["candidates"], out["lookahead_var"] = [], n
+            if device:
+                solver.set_thresholds(thr)
+                res = solver.propagate_pins()
+                thr = solver.thresholds()
+            else:
+                thr, res = propagate_pins(n, offsets, literals, thr)
+            if res["status"] == N.PROP_CONFLICT:
+                out["status"] = "conflict"
+                break
+            S, split = solver.var_scores() if device else var_scores(n, offsets, literals, thr)
+            if split["n_open"] == 0:
+                out["status"] = "satisfied"
+                break
+            T = S[0::2].astype(np.int64) + S[1::2].astype(np.int64)
+            order = np.argsort(-T, kind="stable")[:n_candidates]  # (stable: the lowest variable first on a tie)
+            cands = order[T[order] > 0]
+            probes = np.stack([2 * cands, 2 * cands + 1], 1).astype(np.uint32).ravel()
+            if device:
+                results, pm, pv = solver.probe(probes, rows=True)
+            else:
+                results, pm, pv = probe_literals(n, offsets, literals, thr, probes, rows=True)
+            out["candidates"] = [(int(v), results[2 * i], results[2 * i + 1]) for i, v in enumerate(cands)]
+            status = [(rp["status"], rn["status"]) for _, rp, rn in out["candidates"]]
+            if any(sp == N.PROP_CONFLICT and sn == N.PROP_CONFLICT for sp, sn in status):
+                out["status"] = "conflict"
+                break
+            new = {}
+            for (v, _, _), (sp, sn) in zip(out["candidates"], status):
+                if sp == N.PROP_CONFLICT or sn == N.PROP_CONFLICT:
+                    new[v] = 0 if sp == N.PROP_CONFLICT else 1
+            out["n_failed"] += len(new)
+            free = (thr != 0) & (thr != 0xFFFFFFFF)
+            best = None
+            for i, ((v, rp, rn), (sp, sn)) in enumerate(zip(out["candidates"], status)):
+                if sp != N.PROP_FIXPOINT or sn != N.PROP_FIXPOINT:
+                    continue
+                key = ((rp["n_forced"] + 1) * (rn["n_forced"] + 1), int(T[v]), -v)
+                if best is None or key > best[0]:
+                    best = (key, v)
+                both = np.unpackbits((pm[2 * i] & pm[2 * i + 1] & ~(pv[2 * i] ^ pv[2 * i + 1])).view(np.uint8),
+                                     bitorder="little")[:n].astype(bool) & free
+                val = np.unpackbits(pv[2 * i].view(np.uint8), bitorder="little")
+                for u in np.flatnonzero(both).tolist():
+                    if u not in new:
+                        new[u] = int(val[u])
+                        out["n_necessary"] += 1
+            if best is not None:
+                out["lookahead_var"] = best[1]
+            if not new:
+                break
+            for u, x in new.items():
+                thr[u] = 0xFFFFFFFF if x else 0
+            if max_passes and out["passes"] >= max_passes:
+                break
+    finally:
+        if solver is not None:
+            solver.close()
+    out["thr"] = thr
+    return out
 
 
 def shard_plan(n_clauses: int, world: int, rank: int):

@@ -330,6 +330,39 @@ typedef struct alll_split_result {
  * wrong n_scores: ALLL_ERR_INVALID_ARG.  (No reference counterpart.) */
 int alll_var_scores(alll_ctx* ctx, uint64_t* scores, uint64_t n_scores, alll_split_result* res);
 
+/* Failed-literal probing: what happens if a literal is pinned, for many literals at
+ * once.  A probe is a literal l = 2v + sign; its result is by definition what alll_pinned_propagate
+ * returns on a copy of the thresholds with l pinned true (thr[v] = 0xFFFFFFFF for l = 2v, 0 for
+ * l = 2v + 1; no thresholds: every variable a fair coin) under the same max_rounds: the six rules
+ * above, unchanged, and the same record -- n_forced does not count the probe's own variable.
+ *  - A probe whose variable the base thresholds already pin, either way: ALLL_PROP_NONE, 0 rounds,
+ *    0 forced, conflict_clause = n_clauses; its rows (below) are the base's pins.
+ *  - Duplicates and both polarities of one variable are allowed: every probe is independent.
+ *  - The base need not be a fixpoint; every probe then repeats the base's own implications (and a
+ *    base in conflict makes every probe a conflict): callers should propagate the base first.
+ * Uses: a probe that ends in ALLL_PROP_CONFLICT is a failed literal (its negation is implied); a
+ * variable pinned to the same value under l and under its complement is a necessary assignment;
+ * n_forced of both branches is a look-ahead measure for the split variable.
+ * The optional rows pm_rows and pv_rows are n_probes x n_words words each, n_words = ceil(n_vars/32):
+ * bit v & 31 of pm_rows[p * n_words + (v >> 5)] says that v is pinned when probe p ends (the base's
+ * pins, the probe's own and the forced ones), the same bit of pv_rows its value; after a conflict
+ * that is the state at the start of the conflict round.  Bits past n_vars are 0, pv is 0 where pm
+ * is 0.  A bias is never changed: the rows and the base thresholds give the propagated thresholds
+ * of every probe.
+ * alll_probe_literals runs the probes on the device under the context's current thresholds (none:
+ * every variable free): one pass over the clauses advances 64 probes by a round.  Allowed at any
+ * time: the call drains the stream and changes nothing in the context -- assignment, statistics,
+ * best record, thresholds and the trajectory afterwards are bit for bit those of a context that
+ * never called it.  It refuses the contexts alll_set_var_thresholds refuses, with
+ * ALLL_ERR_UNSUPPORTED before any device work; a null context, null results, null probes with
+ * n_probes != 0, a probe l >= 2 * n_vars (checked for all probes before anything is written), rows
+ * with n_words != ceil(n_vars/32) or a context that belongs to a group: ALLL_ERR_INVALID_ARG.
+ * n_probes == 0: ALLL_OK, nothing is written.  n_probes may be any number: the runtime works in
+ * chunks of 64-probe slabs under a byte budget for its scratch (env ALLL_PROBE_SLABS forces the
+ * chunk's size in slabs, whatever the budget says).  (No group or batch form.  No reference counterpart.) */
+int alll_probe_literals(alll_ctx* ctx, const uint32_t* probes, uint64_t n_probes, uint64_t max_rounds,
+                        alll_propagate_result* results, uint32_t* pm_rows, uint32_t* pv_rows, uint64_t n_words);
+
 /* The residual formula under the pins: what is left of the instance once the
  * pinned variables are decided.  The literal states under thresholds thr are those of the propagation
  * above (true, false, free; a bias that is not a pin is free); without thresholds every variable is
@@ -660,6 +693,15 @@ int alll_pinned_conflict(const alll_problem* prob, const uint32_t* thr, uint64_t
  * alll_pinned_conflict reports the same clause. */
 int alll_pinned_propagate(const alll_problem* prob, uint32_t* thr, uint64_t n, uint64_t max_rounds,
                           alll_propagate_result* res);
+
+/* The probes of alll_probe_literals on the host (the semantics above) under thresholds thr (n ==
+ * n_vars entries; thr == NULL: every variable a fair coin, n is not looked at): one
+ * alll_pinned_propagate per probe.  results: n_probes records; pm_rows, pv_rows: NULL, or n_probes x
+ * ceil(n_vars/32) words each.  Validation and error codes are those of alll_pinned_scores; null
+ * probes with n_probes != 0 or a probe l >= 2 * n_vars: ALLL_ERR_INVALID_ARG; nothing is written on
+ * an error. */
+int alll_pinned_probe(const alll_problem* prob, const uint32_t* thr, uint64_t n, const uint32_t* probes, uint64_t n_probes,
+                      uint64_t max_rounds, alll_propagate_result* results, uint32_t* pm_rows, uint32_t* pv_rows);
 
 /* The split scores of alll_var_scores on the host (the semantics above) under thresholds thr (n ==
  * n_vars entries; thr == NULL: every variable free, n is not looked at).  scores: NULL, or 2 * n_vars
