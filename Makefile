@@ -13,12 +13,12 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 LIB := $(PKG)/liballl.so
 OBJS := $(SRC)/alll_kernels.o $(SRC)/alll_stream.o $(SRC)/alll_refrng.o $(SRC)/alll_runtime.o $(SRC)/alll_layout.o $(SRC)/alll_host.o \
         $(SRC)/alll_small.o $(SRC)/alll_batch.o $(SRC)/alll_batch_runtime.o $(SRC)/alll_propagate.o $(SRC)/alll_score.o $(SRC)/alll_probe.o $(SRC)/alll_residual.o \
-        $(SRC)/alll_group.o $(SRC)/alll_group_runtime.o
+        $(SRC)/alll_group.o $(SRC)/alll_group_probe.o $(SRC)/alll_group_runtime.o
 GROUP_H := $(SRC)/alll_group.h $(SRC)/alll_group_dev.h
 PROP_H := $(SRC)/alll_propagate.h
 SCORE_H := $(SRC)/alll_score.h
 RESID_H := $(SRC)/alll_residual.h
-PROBE_H := $(SRC)/alll_probe.h
+PROBE_H := $(SRC)/alll_probe.h $(SRC)/alll_group_probe.h
 
 all: $(LIB)
 
@@ -72,7 +72,11 @@ $(SRC)/alll_batch_runtime.o: $(SRC)/alll_batch_runtime.cpp $(SRC)/alll_small.h $
 $(SRC)/alll_group.o: $(SRC)/alll_group.cpp $(SRC)/alll_group.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(SRC)/alll_group_runtime.o: $(SRC)/alll_group_runtime.cpp $(GROUP_H) $(PROP_H) $(SCORE_H) $(RESID_H) $(SRC)/alll_internal.h $(SRC)/alll_rt_util.h include/alll.h
+# probing of a whole group: the host-only planner (the kernels are in alll_probe.hip)
+$(SRC)/alll_group_probe.o: $(SRC)/alll_group_probe.cpp $(SRC)/alll_group_probe.h $(SRC)/alll_group.h include/alll.h
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
+$(SRC)/alll_group_runtime.o: $(SRC)/alll_group_runtime.cpp $(GROUP_H) $(PROP_H) $(SCORE_H) $(RESID_H) $(PROBE_H) $(SRC)/alll_internal.h $(SRC)/alll_rt_util.h include/alll.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 # (linked to a temporary name and renamed: a tree snapshot taken meanwhile sees the old or the new library)

@@ -9,7 +9,7 @@ from .solver import (BatchSolver, Clause, GroupSolver, SATInstance, Solver, Stat
                      batch_fits, solve_portfolio, solve_cubes, solve_cubes_propagated, cube_thresholds, pinned_conflict, propagate_pins, var_thresholds,
                      biased_initial_assignment, var_scores, split_cubes, solve_cubes_split,
                      residual_instance, lift_assignment, solve_cubes_residual,
-                     probe_literals, failed_literal_reduce,
+                     probe_literals, failed_literal_reduce, split_cubes_lookahead, solve_cubes_lookahead,
                      assignment_digest, comm_unique_id, device_count, generate_ksat, generate_mixed, gloo_exchange,
                      parse_dimacs,
                      read_dimacs, shard_plan, plan_multi_gpu)

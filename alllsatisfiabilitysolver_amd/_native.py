@@ -75,7 +75,7 @@ EXPORTED = [
     "alll_batch_propagate_pins", "alll_batch_get_var_thresholds",
     "alll_pinned_scores", "alll_var_scores", "alll_group_var_scores",
     "alll_pinned_residual", "alll_residual", "alll_group_residual",
-    "alll_pinned_probe", "alll_probe_literals",
+    "alll_pinned_probe", "alll_probe_literals", "alll_group_probe_literals",
 ]
 
 
@@ -287,6 +287,8 @@ _SIGS = {
                            ctypes.POINTER(PropagateResult), _u32p, _u32p], ctypes.c_int),
     "alll_probe_literals": ([_vp, _u32p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(PropagateResult), _u32p, _u32p,
                              ctypes.c_uint64], ctypes.c_int),
+    "alll_group_probe_literals": ([_vp, _u32p, _u64p, ctypes.c_uint64, ctypes.POINTER(PropagateResult), _u32p, _u32p,
+                                   ctypes.c_uint64], ctypes.c_int),
 }
 
 _lib = None

@@ -14,6 +14,8 @@
 #include "alll.h"
 #include "alll_group.h"
 #include "alll_group_dev.h"
+#include "alll_group_probe.h"
+#include "alll_probe.h"
 #include "alll_propagate.h"
 #include "alll_rt_util.h"
 #include "alll_residual.h"
@@ -407,6 +409,27 @@ int alll_group_residual(alll_group* g, alll_residual_result* results, uint64_t* 
         n_lits = last;
     }
     return resid_drive(p, items, n_lits, results, ResidOut{offsets, literals, var_map, clause_map, thr_out}, g->stream);
+}
+
+// Failed-literal probing of every item at once: the call is validated and laid out on
+// the host (plan_group_probes), then the probe kernels' group forms run over the union with scratch of
+// their own on the drained stream; nothing of the group is written.
+int alll_group_probe_literals(alll_group* g, const uint32_t* probes, const uint64_t* probe_offsets, uint64_t max_rounds,
+                              alll_propagate_result* results, uint32_t* pm_rows, uint32_t* pv_rows, uint64_t n_row_words) {
+    if (!g || !results || !probe_offsets) return fail(ALLL_ERR_INVALID_ARG, "group probes: null argument");
+    int rc;
+    if ((rc = ctx_bias_supported(g->ctx))) return rc;
+    if (!pm_rows != !pv_rows) return fail(ALLL_ERR_INVALID_ARG, "group probes: the two row arrays go together");
+    const CtxAccess a = ctx_access(g->ctx);
+    GroupProbePlan plan;
+    if ((rc = plan_group_probes(g->items.data(), g->items.size(), a.b->n_vars, probes, probe_offsets, pm_rows != nullptr,
+                                n_row_words, probe_forced_chunk(), PROBE_BUDGET_BYTES, plan)))
+        return fail(rc, "%s", plan.err.c_str());
+    if (plan.n_probes == 0) return ALLL_OK;
+    HIP_TRY(hipSetDevice(g->device));
+    PropArgs p{};
+    if ((rc = group_prop_args(g, a, &p))) return rc;
+    return group_probe_drive(p, plan, g->items.data(), probes, max_rounds, results, pm_rows, pv_rows, g->stream);
 }
 
 int alll_group_get_var_thresholds(alll_group* g, uint64_t item, uint32_t* out, uint64_t n) {

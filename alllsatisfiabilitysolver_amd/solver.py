@@ -778,6 +778,39 @@ class GroupSolver(_ItemSolver):
         cuts = np.cumsum([2 * n for n in self.n_vars])[:-1]
         return [res[i].as_dict() for i in range(self.n_items)], np.split(scores, cuts)
 
+    def probes(self, probes, max_rounds: int = 0, rows: bool = False) -> list:
+        """alll_group_probe_literals: Solver.probe for every item in one call -- the items' variables are
+        disjoint, so one pass over the union's clauses advances 64 probes of every item.  probes: one
+        sequence of literals per item, in the item's own numbering (an empty one: the item is not
+        probed); max_rounds is the call's.  At any time; nothing of the group changes.  Returns a list
+        with, per item, what Solver.probe returns: the list of result dicts, or with rows=True (results,
+        pm, pv), uint32[n_probes_i, n_words_i] each."""
+        per = [np.ascontiguousarray(q, np.uint32).ravel() for q in probes]
+        if len(per) != self.n_items:
+            raise ValueError(f"{len(per)} probe lists for {self.n_items} items")
+        offs = np.zeros(self.n_items + 1, np.uint64)
+        offs[1:] = np.cumsum([q.size for q in per])
+        flat = np.concatenate(per) if per else np.zeros(0, np.uint32)
+        total = int(offs[-1])
+        res = (N.PropagateResult * max(1, total))()
+        nws = [(n + 31) // 32 for n in self.n_vars]
+        n_row_words = sum(q.size * nw for q, nw in zip(per, nws))
+        pm = np.zeros(n_row_words, np.uint32) if rows else None
+        pv = np.zeros(n_row_words, np.uint32) if rows else None
+        N.check(self._L.alll_group_probe_literals(self._h, _p(flat, _u32p), _p(offs, _u64p), max_rounds, res,
+                                                  _p(pm, _u32p) if rows else None, _p(pv, _u32p) if rows else None,
+                                                  n_row_words), "alll_group_probe_literals")
+        out, at = [], 0
+        for i, (q, nw) in enumerate(zip(per, nws)):
+            first = int(offs[i])
+            r = [res[first + j].as_dict() for j in range(q.size)]
+            if rows:
+                out.append((r, pm[at:at + q.size * nw].reshape(q.size, nw), pv[at:at + q.size * nw].reshape(q.size, nw)))
+                at += q.size * nw
+            else:
+                out.append(r)
+        return out
+
     def residuals(self, with_arrays: bool = True) -> List[dict]:
         """alll_group_residual: Solver.residual for every item in one pass over the union.  Returns one
         dict per item, in the item's own clause and variable numbering; an item without thresholds has
@@ -994,6 +1027,46 @@ def solve_cubes_split(n_vars: int, offsets, literals, depth: int, base=(), seeds
     return leaves, ((None, None, None) if win is None else (live[win], st, words))
 
 
+def _lookahead_candidates(S, n_candidates: int):
+    """Step 3 and 4 of failed_literal_reduce from the scores S -> (T, the candidates, their probes)."""
+    T = S[0::2].astype(np.int64) + S[1::2].astype(np.int64)
+    order = np.argsort(-T, kind="stable")[:n_candidates]  # (stable: the lowest variable first on a tie)
+    cands = order[T[order] > 0]
+    probes = np.stack([2 * cands, 2 * cands + 1], 1).astype(np.uint32).ravel()
+    return T, cands, probes
+
+
+def _lookahead_judge(n: int, thr, T, cands, results, pm, pv):
+    """Steps 5 to 7 of failed_literal_reduce from the candidates' probes -> (candidates, conflict, the
+    pass's new pins {variable: value}, failed literals, necessary assignments, lookahead_var); with
+    conflict nothing after it is counted."""
+    candidates = [(int(v), results[2 * i], results[2 * i + 1]) for i, v in enumerate(cands)]
+    status = [(rp["status"], rn["status"]) for _, rp, rn in candidates]
+    if any(sp == N.PROP_CONFLICT and sn == N.PROP_CONFLICT for sp, sn in status):
+        return candidates, True, {}, 0, 0, n
+    new = {}
+    for (v, _, _), (sp, sn) in zip(candidates, status):
+        if sp == N.PROP_CONFLICT or sn == N.PROP_CONFLICT:
+            new[v] = 0 if sp == N.PROP_CONFLICT else 1
+    n_failed, n_necessary = len(new), 0
+    free = (thr != 0) & (thr != 0xFFFFFFFF)
+    best = None
+    for i, ((v, rp, rn), (sp, sn)) in enumerate(zip(candidates, status)):
+        if sp != N.PROP_FIXPOINT or sn != N.PROP_FIXPOINT:
+            continue
+        key = ((rp["n_forced"] + 1) * (rn["n_forced"] + 1), int(T[v]), -v)
+        if best is None or key > best[0]:
+            best = (key, v)
+        both = np.unpackbits((pm[2 * i] & pm[2 * i + 1] & ~(pv[2 * i] ^ pv[2 * i + 1])).view(np.uint8),
+                             bitorder="little")[:n].astype(bool) & free
+        val = np.unpackbits(pv[2 * i].view(np.uint8), bitorder="little")
+        for u in np.flatnonzero(both).tolist():
+            if u not in new:
+                new[u] = int(val[u])
+                n_necessary += 1
+    return candidates, False, new, n_failed, n_necessary, n if best is None else best[1]
+
+
 def failed_literal_reduce(n_vars: int, offsets, literals, thr=None, n_candidates: int = 64, max_passes: int = 0,
                           device: bool = True) -> dict:
     """Failed-literal and necessary-assignment reduction of thresholds thr (None: every variable a fair
@@ -1042,41 +1115,18 @@ def failed_literal_reduce(n_vars: int, offsets, literals, thr=None, n_candidates
             if split["n_open"] == 0:
                 out["status"] = "satisfied"
                 break
-            T = S[0::2].astype(np.int64) + S[1::2].astype(np.int64)
-            order = np.argsort(-T, kind="stable")[:n_candidates]  # (stable: the lowest variable first on a tie)
-            cands = order[T[order] > 0]
-            probes = np.stack([2 * cands, 2 * cands + 1], 1).astype(np.uint32).ravel()
+            T, cands, probes = _lookahead_candidates(S, n_candidates)
             if device:
                 results, pm, pv = solver.probe(probes, rows=True)
             else:
                 results, pm, pv = probe_literals(n, offsets, literals, thr, probes, rows=True)
-            out["candidates"] = [(int(v), results[2 * i], results[2 * i + 1]) for i, v in enumerate(cands)]
-            status = [(rp["status"], rn["status"]) for _, rp, rn in out["candidates"]]
-            if any(sp == N.PROP_CONFLICT and sn == N.PROP_CONFLICT for sp, sn in status):
+            out["candidates"], conflict, new, n_failed, n_necessary, look = _lookahead_judge(n, thr, T, cands, results, pm, pv)
+            if conflict:
                 out["status"] = "conflict"
                 break
-            new = {}
-            for (v, _, _), (sp, sn) in zip(out["candidates"], status):
-                if sp == N.PROP_CONFLICT or sn == N.PROP_CONFLICT:
-                    new[v] = 0 if sp == N.PROP_CONFLICT else 1
-            out["n_failed"] += len(new)
-            free = (thr != 0) & (thr != 0xFFFFFFFF)
-            best = None
-            for i, ((v, rp, rn), (sp, sn)) in enumerate(zip(out["candidates"], status)):
-                if sp != N.PROP_FIXPOINT or sn != N.PROP_FIXPOINT:
-                    continue
-                key = ((rp["n_forced"] + 1) * (rn["n_forced"] + 1), int(T[v]), -v)
-                if best is None or key > best[0]:
-                    best = (key, v)
-                both = np.unpackbits((pm[2 * i] & pm[2 * i + 1] & ~(pv[2 * i] ^ pv[2 * i + 1])).view(np.uint8),
-                                     bitorder="little")[:n].astype(bool) & free
-                val = np.unpackbits(pv[2 * i].view(np.uint8), bitorder="little")
-                for u in np.flatnonzero(both).tolist():
-                    if u not in new:
-                        new[u] = int(val[u])
-                        out["n_necessary"] += 1
-            if best is not None:
-                out["lookahead_var"] = best[1]
+            out["n_failed"] += n_failed
+            out["n_necessary"] += n_necessary
+            out["lookahead_var"] = look
             if not new:
                 break
             for u, x in new.items():
@@ -1088,6 +1138,143 @@ def failed_literal_reduce(n_vars: int, offsets, literals, thr=None, n_candidates
             solver.close()
     out["thr"] = thr
     return out
+
+
+def _lookahead_split(n: int, S, lookahead_var: int):
+    """The split variable of a look-ahead node and its preferred literal from the scores S under the
+    node's reduced thresholds: lookahead_var, else (n: no candidate's probes both ended in a fixpoint) the
+    arg-max of S[2v] + S[2v+1], the lowest variable on a tie."""
+    v = int(lookahead_var)
+    if v == n:
+        v = int(np.argmax(S[0::2].astype(np.int64) + S[1::2].astype(np.int64)))
+    return v, 2 * v + (0 if int(S[2 * v]) >= int(S[2 * v + 1]) else 1)
+
+
+def split_cubes_lookahead(n_vars: int, offsets, literals, depth: int, base=(), n_candidates: int = 32, device: int = -1,
+                          host: bool = False):
+    """split_cubes with look-ahead: the same tree and leaf order, but a node first reduces its thresholds
+    with r = failed_literal_reduce(thr, n_candidates, max_passes=0): r["status"] "conflict" is a dead leaf
+    (thr None), "satisfied" a satisfied one; at `depth` the node is an open leaf with r["thr"]; else it
+    splits on r["lookahead_var"] (the arg-max of the scores under r["thr"] when there is none), preferred
+    literal 2v when S[2v] >= S[2v+1] else 2v + 1, first child the preferred literal.  Returns the leaves
+    {"cube", "status", "thr", "n_failed", "n_necessary", "passes"}, the last three r's.
+    host=False: one GroupSolver of 2^depth items in lockstep -- per level, passes of propagate_pins,
+    var_scores and one GroupSolver.probes call for all items, until no item pins anything new; at level
+    l only the 2^l items whose low depth - l bits are 0 probe, the others copy their thresholds.
+    host=True: the same tree from failed_literal_reduce(device=False) and var_scores, no device touched.
+    Integers and fixed tie rules only: both return equal lists.  1 <= depth <= 10, n_candidates >= 1."""
+    if not 1 <= int(depth) <= 10:
+        raise ValueError(f"depth {depth} is not in 1 .. 10")
+    if int(n_candidates) < 1:
+        raise ValueError("n_candidates must be at least 1")
+    depth, n_candidates, n = int(depth), int(n_candidates), int(n_vars)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    literals = np.ascontiguousarray(literals, np.uint32)
+    base = [int(l) for l in base]
+    thr0 = cube_thresholds(n, base)
+    pin = lambda d: 0 if d & 1 else 0xFFFFFFFF  # noqa: E731
+    if host:
+        leaves = []
+
+        def node(cube, thr, level):
+            r = failed_literal_reduce(n, offsets, literals, thr, n_candidates, 0, device=False)
+            leaf = {"cube": cube, "status": r["status"], "thr": None if r["status"] == "conflict" else r["thr"],
+                    "n_failed": r["n_failed"], "n_necessary": r["n_necessary"], "passes": r["passes"]}
+            if r["status"] != "open" or level == depth:
+                leaves.append(leaf)
+                return
+            S, _ = var_scores(n, offsets, literals, r["thr"])
+            v, p = _lookahead_split(n, S, r["lookahead_var"])
+            for b in (0, 1):
+                t = r["thr"].copy()
+                t[v] = pin(p ^ b)
+                node(cube + [p ^ b], t, level + 1)
+
+        node(list(base), thr0, 0)
+        return leaves
+    n_items = 1 << depth
+    cubes = [list(base) for _ in range(n_items)]
+    leaf: List[Optional[dict]] = [None] * n_items  # (None: live)
+    count = [{"n_failed": 0, "n_necessary": 0, "passes": 0} for _ in range(n_items)]
+    with GroupSolver([(n, offsets, literals)] * n_items, range(1, n_items + 1), device=device) as g:
+        for i in range(n_items):
+            g.set_thresholds(i, thr0)
+        for level in range(depth + 1):
+            span = 1 << (depth - level)
+            reps = [i for i in range(0, n_items, span) if leaf[i] is None]
+            for i in reps:
+                count[i] = {"n_failed": 0, "n_necessary": 0, "passes": 0}
+            done = {}  # representative -> (status, thr, scores, lookahead_var) once its reduction has ended
+            while len(done) < len(reps):
+                todo = [i for i in reps if i not in done]
+                res = g.propagate_pins()
+                for i in todo:
+                    count[i]["passes"] += 1
+                    if res[i]["status"] == N.PROP_CONFLICT:
+                        done[i] = ("conflict", None, None, n)
+                todo = [i for i in todo if i not in done]
+                if not todo:
+                    break
+                split, scores = g.var_scores(with_scores=True)
+                probes, look = [()] * n_items, {}
+                for i in todo:
+                    if split[i]["n_open"] == 0:
+                        done[i] = ("satisfied", g.thresholds(i), None, n)
+                    else:
+                        look[i] = _lookahead_candidates(scores[i], n_candidates)
+                        probes[i] = look[i][2]
+                todo = [i for i in todo if i not in done]
+                if not todo:
+                    break
+                out = g.probes(probes, rows=True)
+                for i in todo:
+                    thr = g.thresholds(i)
+                    T, cands, _ = look[i]
+                    _, conflict, new, n_failed, n_necessary, var = _lookahead_judge(n, thr, T, cands, *out[i])
+                    if conflict:
+                        done[i] = ("conflict", None, None, n)
+                        continue
+                    count[i]["n_failed"] += n_failed
+                    count[i]["n_necessary"] += n_necessary
+                    if not new:
+                        done[i] = ("open", thr, scores[i], var)
+                        continue
+                    for u, x in new.items():
+                        thr[u] = 0xFFFFFFFF if x else 0
+                    g.set_thresholds(i, thr)
+            for i in reps:
+                status, thr, S, var = done[i]
+                if status != "open" or level == depth:
+                    for j in range(i, i + span):  # (the items that share the prefix are one leaf)
+                        leaf[j] = dict(cube=cubes[j], status=status, thr=thr, **count[i])
+                    continue
+                v, p = _lookahead_split(n, S, var)
+                for j in range(i, i + span):
+                    d = p ^ ((j >> (depth - 1 - level)) & 1)
+                    t = thr.copy()
+                    t[v] = pin(d)
+                    g.set_thresholds(j, t)
+                    cubes[j].append(d)
+    leaves, seen = [], set()
+    for i in range(n_items):
+        if tuple(cubes[i]) not in seen:
+            seen.add(tuple(cubes[i]))
+            leaves.append(leaf[i])
+    return leaves
+
+
+def solve_cubes_lookahead(n_vars: int, offsets, literals, depth: int, base=(), n_candidates: int = 32, seeds=None,
+                          max_iters: int = 0):
+    """solve_cubes_split on the leaves of split_cubes_lookahead: the cubes of the leaves that are not in
+    conflict go, in leaf order, through solve_cubes_propagated (seeds: None, or one per such leaf).
+    Returns (leaves, (leaf index, stats, assignment_words)): the winner's index in `leaves`;
+    (leaves, (None, None, None)) when no leaf is left or max_iters capped every one."""
+    leaves = split_cubes_lookahead(n_vars, offsets, literals, depth, base, n_candidates)
+    live = [j for j, leaf in enumerate(leaves) if leaf["status"] != "conflict"]
+    if not live:
+        return leaves, (None, None, None)
+    win, st, words = solve_cubes_propagated(n_vars, offsets, literals, [leaves[j]["cube"] for j in live], seeds, max_iters)
+    return leaves, ((None, None, None) if win is None else (live[win], st, words))
 
 
 def shard_plan(n_clauses: int, world: int, rank: int):

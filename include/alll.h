@@ -359,7 +359,8 @@ int alll_var_scores(alll_ctx* ctx, uint64_t* scores, uint64_t n_scores, alll_spl
  * with n_words != ceil(n_vars/32) or a context that belongs to a group: ALLL_ERR_INVALID_ARG.
  * n_probes == 0: ALLL_OK, nothing is written.  n_probes may be any number: the runtime works in
  * chunks of 64-probe slabs under a byte budget for its scratch (env ALLL_PROBE_SLABS forces the
- * chunk's size in slabs, whatever the budget says).  (No group or batch form.  No reference counterpart.) */
+ * chunk's size in slabs, whatever the budget says).  (The group form is alll_group_probe_literals,
+ * declared with the groups; no batch form.  No reference counterpart.) */
 int alll_probe_literals(alll_ctx* ctx, const uint32_t* probes, uint64_t n_probes, uint64_t max_rounds,
                         alll_propagate_result* results, uint32_t* pm_rows, uint32_t* pv_rows, uint64_t n_words);
 
@@ -619,6 +620,26 @@ int alll_group_residual(alll_group* g, alll_residual_result* results, uint64_t* 
 int alll_group_track_best(alll_group* g, int on);
 int alll_group_get_best(alll_group* g, uint64_t item, uint64_t* n_violated, uint64_t* iteration, uint32_t* words,
                         uint64_t n_words);
+/* alll_probe_literals for every item of a group at once.  Item i owns
+ * probes[probe_offsets[i] .. probe_offsets[i + 1]) (n_items + 1 offsets from 0, not descending; an item
+ * may have none), literals in the item's own numbering.  results[probe_offsets[i] + j] is exactly what
+ * alll_probe_literals returns for that probe on a context of its own created from the item and given
+ * the item's thresholds (none: every variable free): status, rounds and n_forced; conflict_clause is
+ * the item's own index, its n_clauses when there is none.  max_rounds is one value for the call.  The
+ * items' variables are disjoint, so one pass over the union's clauses advances 64 probes of every item.
+ * The rows are optional and go together (both NULL or neither): item after item, item i's block is
+ * n_probes_i x n_words_i words, n_words_i = ceil(n_vars_i / 32) with no padding to the union, row j
+ * with the contract above; n_row_words must be the sum of the blocks when rows are given.
+ * The contract is alll_group_var_scores': allowed at any time, the stream is drained, nothing in the
+ * group changes; refused like alll_group_set_var_thresholds, with ALLL_ERR_UNSUPPORTED before any
+ * device work.  ALLL_ERR_INVALID_ARG, nothing written: a null group, results or offsets; null probes
+ * with a non-zero total; offsets that do not start at 0 or descend; one row array without the other;
+ * a probe l >= 2 * n_vars of its own item (checked for all probes first -- such a literal can be a
+ * valid one of the union); a wrong n_row_words.  No probes at all: ALLL_OK, nothing written.  Works in
+ * chunks of layers (layer L: probes 64 L .. 64 L + 63 of every item that has them) under the byte
+ * budget of alll_probe_literals; env ALLL_PROBE_SLABS forces the layers per chunk. */
+int alll_group_probe_literals(alll_group* g, const uint32_t* probes, const uint64_t* probe_offsets, uint64_t max_rounds,
+                              alll_propagate_result* results, uint32_t* pm_rows, uint32_t* pv_rows, uint64_t n_row_words);
 /* alll_layout / alll_eval_kernel / alll_epoch_counters of the union. */
 int alll_group_layout(alll_group* g);
 const char* alll_group_eval_kernel(alll_group* g);
